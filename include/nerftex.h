@@ -479,7 +479,10 @@ int ntx_instancer_set_mesh_textures(ntx_instancer *inst, const float *uv, int64_
  * Replaces the body of the reference's training loop, network/train.py:61-67: `pred = renderer(**data)` under a GradientTape, a loss
  * of network/loss.py:6-59, `tape.gradient`, `optimizer.apply_gradients` with tf.keras.optimizers.Adam under ExponentialDecay
  * (train.py:49-52).  Built for the architecture of the shipped training configs: ParamNerf, depth 8, width 256, skips [4],
- * color_depth 1, Fourier features (any n_parameters, any band counts); NTX_E_UNSUPPORTED otherwise.  The trainer owns the weights
+ * color_depth 1, Fourier features on n_pos 3 (any n_parameters, any band counts) or -- the MipRenderer's model -- NTX_POS_IPE on n_pos 6
+ * (pos_map = 6 pos_freq + n_geo (1 + 2 param_freq) features; ntx_weight_count of the same descriptor); NTX_E_UNSUPPORTED otherwise.  An IPE
+ * trainer has no importance pass: ntx_trainer_composite_weights refuses it (NTX_E_UNSUPPORTED), as the reference's MipRenderer refuses
+ * n_importance > 0 (renderer.py:403-404).  The trainer owns the weights
  * (Keras get_weights() order, like ntx_create), Adam's moments, the gradient and every layer's activations for up to
  * max_rays x max_samples_per_ray samples (<= 1024 samples per ray; 23 KB per sample: 6 GB for the configs' 4 x 256 x 256; pos_map and
  * dir_map at most 96 features wide each).  Everything float32.  A step is bit-reproducible: weight gradients are summed over the samples
@@ -526,7 +529,12 @@ int ntx_trainer_activation(ntx_trainer *t, int layer, int64_t n_samples_total, f
  * NTX_FLAG_COMPOSITE_BKGD), the loss, and its gradient with respect to every weight, left in the trainer (ntx_trainer_get /
  * ntx_trainer_adam_step).  DEVICE: rays_o[N,3], rays_d[N,3], tnear_far[N,2] (or NULL with z_vals), params[rows,P] (ray r uses row
  * r / rays_per_param_row), cone_scale[N] (blur_idx >= 0), color_true[N,3], alpha_true[N] (AlphaLoss); outputs, each may be NULL:
- * color_pred[N,3], alpha_pred[N], loss_out[1].  bkgd: HOST [3] or NULL (white). */
+ * color_pred[N,3], alpha_pred[N], loss_out[1].  bkgd: HOST [3] or NULL (white).
+ * An IPE trainer follows MipRenderer.render_rays (renderer.py:365-473): n_samples = S cone segments between S + 1 depths --
+ * ntx_sample_depths(n_points = S + 1) under the same flags and seed, or z_vals[N,S+1] -- each encoded by its gaussian (mean, diagonal
+ * covariance) through the integrated positional encoding (layer.py:25-41); params[rows,P+1] hold the blur parameter at blur_idx (required,
+ * 0 <= blur_idx <= P): times cone_scale it is the cone's radius, and the model sees the other P (column k < blur_idx ? k : k + 1); the
+ * composite's dists are z[s+1] - z[s] with no copy of the last one. */
 int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
                              const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
                              const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,

@@ -381,12 +381,63 @@ __global__ __launch_bounds__(64) void encode_kernel(EncodeArgs a) {
     }
 }
 
+// encode_kernel for the MipRenderer (renderer.py:365-444) and an IntegratedPositionalEncoding model (layer.py:25-41): sample s is the cone segment
+// between edges z[s] and z[s+1] of the ray's S + 1 depths (z is [N][S+1]), encoded as the gaussian of cone_moments / cone_cov (ntx_device.h,
+// the render kernel's own) with radius params[blur_idx] * cone_scale; the blur parameter is spliced out of the rows of P + 1 values and the model
+// sees the other P.  pos_map = [sin(2^f mean_c) exp(-4^f cov_c / 2) for f, c band-major | the same with cos] | FourierFeatures(geometry
+// parameters); dists = (z[s+1] - z[s]) |rays_d| with no copy of the last one (:441-444).  A ray that misses the proxy encodes mean = o, cov = 0
+// (finite rows) with dists 0: like the Fourier path's, it composites to 0 / the background and no gradient flows through its rows.
+__global__ __launch_bounds__(64) void encode_ipe_kernel(EncodeArgs a) {
+    const int lane = threadIdx.x, n = lane & 31, h = lane >> 5, blk = blockIdx.x, part = blockIdx.y;
+    const long long m = (long long)blk * 32 + n;
+    const bool valid = m < a.M;
+    const int ray = valid ? (int)(m / a.S) : 0, s = valid ? (int)(m - (long long)ray * a.S) : 0;
+    const float d[3] = {a.rays_d[3 * ray], a.rays_d[3 * ray + 1], a.rays_d[3 * ray + 2]};
+    const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    const float *zr = a.z + (size_t)ray * (a.S + 1) + s;
+    const float e0 = zr[0], e1 = zr[1];
+    const bool hit = isfinite(e0) && isfinite(e1);
+    const int P = a.n_geo + a.n_app;
+    const float *pr = a.params + (size_t)(ray / a.rays_per_param_row) * (P + 1);
+    auto param = [&](int k) { return pr[k < a.blur_idx ? k : k + 1]; };             // renderer.py:386
+    float *O = part == 0 ? a.posO : a.dirO;
+    const int tiles = part == 0 ? a.ptiles : a.dtiles;
+    auto put = [&](int row, float v) {
+        if (!valid) v = 0.0f;
+        O[(((size_t)blk * tiles + (row >> 5)) * 4 + (n >> 3)) * 256 + ((row & 31) + 32 * ((n >> 2) & 1)) * 4 + (n & 3)] = v;
+    };
+    auto fourier = [&](int r0, int D, int L, auto x) {
+        if (h == 0) for (int c = 0; c < D; ++c) put(r0 + c, x(c));
+        for (int f = 0; f < L; ++f)
+            for (int c = 0; c < D; ++c) put(r0 + D + 2 * D * f + h * D + c, ntx::sin_q(ldexpf(1.0f, f) * x(c), h));
+    };
+    if (part == 0) {
+        float mean[3] = {a.rays_o[3 * ray], a.rays_o[3 * ray + 1], a.rays_o[3 * ray + 2]}, cov[3] = {0.0f, 0.0f, 0.0f};
+        if (hit) {                                                                              // renderer.py:411-437
+            float t_mean, t_var, r_var;
+            ntx::cone_moments((e0 + e1) / 2.0f, (e1 - e0) / 2.0f, pr[a.blur_idx] * a.cone[ray], t_mean, t_var, r_var);
+            for (int c = 0; c < 3; ++c) mean[c] = mean[c] + d[c] * t_mean;
+            ntx::cone_cov(t_var, r_var, d, cov);
+        }
+        const int L = a.pos_freq;
+        for (int f = 0; f < L; ++f)                                                             // layer.py:33-41: row h 3L + 3f + c
+            for (int c = 0; c < 3; ++c)
+                put(h * 3 * L + 3 * f + c, ntx::sin_q(mean[c] * ldexpf(1.0f, f), h) * expf(-0.5f * (cov[c] * ldexpf(1.0f, 2 * f))));
+        if (a.n_geo > 0) fourier(6 * L, a.n_geo, a.param_freq, [&](int c) { return param(c); });          // model.py:88-93
+    } else {
+        fourier(0, 3, a.dir_freq, [&](int c) { return d[c] / dn; });
+        if (a.n_app > 0) fourier(3 * (1 + 2 * a.dir_freq), a.n_app, a.param_freq, [&](int c) { return param(a.n_geo + c); });
+        if (valid && h == 0) a.dists[(size_t)ray * a.S + s] = hit ? (e1 - e0) * dn : 0.0f;
+    }
+}
+
 // The colour layer's direction segment once per ray (fwd_chain_kernel's HOIST builds): row[f] = bias_C1[f] + sum_k dir_map[k] W_C1[k][f] over
 // the Kd rows of dir_map = FourierFeatures(direction) | FourierFeatures(appearance parameters) (model.py:96-101, 115), written in the
 // accumulators' order [ray][half h][16 T + 4 g + c] for feature 32 T + 8 g + 4 h + c.  Workgroup per ray, thread per output feature.
+// splice >= 0 (the MipRenderer): the parameter rows hold P + 1 values and model parameter k is column k < splice ? k : k + 1 (encode_ipe_kernel).
 struct DirRowArgs {
     const float *rays_d, *params; long long rays_per_param_row;
-    int n_rays, n_geo, n_app, dir_freq, param_freq, Kd;
+    int n_rays, n_geo, n_app, dir_freq, param_freq, Kd, splice;
     const float *w, *bias;                     // W_C1 [Kd + 256][256] (its first Kd rows), bias_C1 [256]
     float *rows;
 };
@@ -395,12 +446,12 @@ __global__ __launch_bounds__(256) void dirrow_kernel(DirRowArgs a) {
     const int ray = blockIdx.x, f = threadIdx.x;
     const float d[3] = {a.rays_d[3 * ray], a.rays_d[3 * ray + 1], a.rays_d[3 * ray + 2]};
     const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const int P = a.n_geo + a.n_app;
+    const int P = a.n_geo + a.n_app + (a.splice >= 0 ? 1 : 0);
     const float *pr = a.params + (size_t)(ray / a.rays_per_param_row) * (P > 0 ? P : 1);
     if (f < a.Kd) {                                                                             // row f of dir_map, as encode_kernel lays it out
         const int K3 = 3 * (1 + 2 * a.dir_freq);
         const int r = f < K3 ? f : f - K3, D = f < K3 ? 3 : a.n_app;
-        auto x = [&](int c) { return f < K3 ? d[c] / dn : pr[a.n_geo + c]; };                  // renderer.py:98; model.py:96-101
+        auto x = [&](int c) { const int k = a.n_geo + c; return f < K3 ? d[c] / dn : pr[a.splice >= 0 && k >= a.splice ? k + 1 : k]; };   // renderer.py:98; model.py:96-101
         float v;
         if (r < D) v = x(r);
         else { const int q = r - D, band = q / (2 * D), hc = q - band * 2 * D, hh = hc / D, c = hc - hh * D; v = ntx::sin_q(ldexpf(1.0f, band) * x(c), hh); }
@@ -586,6 +637,7 @@ struct ntx_trainer {
     int device = 0, cus = 256;
     ntx_model_desc desc{};
     int Kp = 0, Kd = 0, P = 0, ptiles = 0, dtiles = 0, PS = 0, DS = 0;   // pos_map / dir_map: features, tiles of 32 rows of their buffers, k-steps of their segments
+    bool ipe = false;                          // an IntegratedPositionalEncoding model: a MipRenderer step (encode_ipe_kernel)
     TLayer trunk[8], feature, c1, c2, rgb, alpha;
     size_t n_weights = 0;
     long long cap = 0, cap_blocks = 0, cap_rays = 0;   // samples (blocks of 32 samples, rays) the buffers hold
@@ -662,13 +714,14 @@ int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t 
     if (!out) return ntx_set_error(NTX_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!desc || !weights) return ntx_set_error(NTX_E_INVALID, "desc / weights is NULL");
-    if (desc->kind != NTX_MODEL_PARAMNERF || desc->depth != 8 || desc->width != 256 || desc->skip != 4 || desc->color_depth != 1 || desc->n_pos != 3 ||
-        desc->pos_encoding != NTX_POS_FOURIER)
+    const bool ipe = desc->pos_encoding == NTX_POS_IPE && desc->n_pos == 6;        // MipRenderer + IntegratedPositionalEncoding (renderer.py:356-473)
+    if (desc->kind != NTX_MODEL_PARAMNERF || desc->depth != 8 || desc->width != 256 || desc->skip != 4 || desc->color_depth != 1 ||
+        !((desc->pos_encoding == NTX_POS_FOURIER && desc->n_pos == 3) || ipe))
         return ntx_set_error(NTX_E_UNSUPPORTED, "training is built for the ParamNerf architecture of the shipped training configs (depth 8, width 256, skips [4], color_depth 1, "
-                                                "Fourier features); others render but do not train");
+                                                "Fourier features on n_pos 3 or IPE on n_pos 6); others render but do not train");
     if (desc->n_geo < 0 || desc->n_app < 0 || desc->n_geo + desc->n_app > 16) return ntx_set_error(NTX_E_INVALID, "n_parameters out of range");
     if (desc->pos_freq < 0 || desc->dir_freq < 0 || desc->param_freq < 0) return ntx_set_error(NTX_E_INVALID, "negative band count");
-    const int Kp = 3 * (1 + 2 * desc->pos_freq) + desc->n_geo * (1 + 2 * desc->param_freq), Kd = 3 * (1 + 2 * desc->dir_freq) + desc->n_app * (1 + 2 * desc->param_freq);
+    const int Kp = (ipe ? 6 * desc->pos_freq : 3 * (1 + 2 * desc->pos_freq)) + desc->n_geo * (1 + 2 * desc->param_freq), Kd = 3 * (1 + 2 * desc->dir_freq) + desc->n_app * (1 + 2 * desc->param_freq);
     if (Kp > 8 * MAX_PB_GROUPS || Kd > 8 * MAX_PB_GROUPS)
         return ntx_set_error(NTX_E_UNSUPPORTED, "training: pos_map (%d) / dir_map (%d) wider than %d features (the chain holds a block's encoded inputs in registers)", Kp, Kd,
                              8 * MAX_PB_GROUPS);
@@ -678,7 +731,7 @@ int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ntx_set_error(NTX_E_NODEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return ntx_set_error(NTX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
     ntx_trainer *t = new ntx_trainer();
-    t->device = device; t->desc = *desc;
+    t->device = device; t->desc = *desc; t->ipe = ipe;
     t->P = desc->n_geo + desc->n_app; t->Kp = Kp; t->Kd = Kd;
     t->ptiles = (Kp + 31) / 32; t->dtiles = (Kd + 31) / 32;
     {   // the forward chain's build for these segment lengths, or the longest one (the streams are then padded with zero rows)
@@ -713,7 +766,7 @@ int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t 
     alloc(&t->act, (size_t)t->act_stride * 11); alloc((float **)&t->bits, (size_t)t->bits_stride * 10); alloc(&t->gout, (size_t)t->gout_stride * 11);
     auto act = [&](int i) { return t->act + (size_t)i * t->act_stride; };
     auto gout = [&](int i) { return t->gout + (size_t)i * t->gout_stride; };
-    alloc(&t->sigma, (size_t)M); alloc(&t->raw_rgb, (size_t)M * 3); alloc(&t->z, (size_t)M); alloc(&t->dists, (size_t)M); alloc(&t->noise, (size_t)M);
+    alloc(&t->sigma, (size_t)M); alloc(&t->raw_rgb, (size_t)M * 3); alloc(&t->z, (size_t)(M + max_rays)); alloc(&t->dists, (size_t)M); alloc(&t->noise, (size_t)M);
     alloc(&t->dirrow, (size_t)max_rays * 256);
     alloc(&t->dgrad, (size_t)NB * 32 * 4); alloc(&t->dhead, (size_t)NB * 1024, true);       // rows 4 .. 31 of the heads' dY tile stay zero
     alloc(&t->color, (size_t)max_rays * 3); alloc(&t->alpha_out, (size_t)max_rays); alloc(&t->ray_loss, (size_t)max_rays); alloc(&t->loss, 1);
@@ -935,6 +988,7 @@ int ntx_trainer_set_iterations(ntx_trainer *t, int64_t iterations) {
 
 int ntx_trainer_composite_weights(ntx_trainer *t, float *weights_dev) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    if (t->ipe && weights_dev) return ntx_set_error(NTX_E_UNSUPPORTED, "an IPE trainer has no importance pass (MipRenderer: renderer.py:403-404)");
     t->weights_out = weights_dev;
     return NTX_OK;
 }
@@ -975,10 +1029,11 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
                              const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,
                              float *color_pred, float *alpha_pred, float *loss_out, ntx_stream stream) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
-    if (!rays_o || !rays_d || (!tnear_far && !z_vals) || !color_true || !loss || (t->P > 0 && !params)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    const int P_in = t->P + (t->ipe ? 1 : 0);                                               // the MipRenderer's rows still hold the blur parameter
+    if (!rays_o || !rays_d || (!tnear_far && !z_vals) || !color_true || !loss || (P_in > 0 && !params)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
     if (n_rays < 1 || n_rays > t->cap_rays || n_samples < 2 || (long long)n_rays * n_samples > t->cap) return ntx_set_error(NTX_E_INVALID, "n_rays x n_samples beyond what the trainer was created for");
     if (n_samples > MAX_TRAIN_SAMPLES) return ntx_set_error(NTX_E_INVALID, "n_samples > %d", MAX_TRAIN_SAMPLES);
-    if (blur_idx >= t->P || (blur_idx >= 0 && !cone_scale)) return ntx_set_error(NTX_E_INVALID, "bad blur_idx / cone_scale");
+    if (blur_idx >= P_in || (blur_idx >= 0 && !cone_scale) || (t->ipe && blur_idx < 0)) return ntx_set_error(NTX_E_INVALID, "bad blur_idx / cone_scale");
     if (loss->size < sizeof(ntx_loss_desc) || (loss->kind != NTX_LOSS_NERF && loss->kind != NTX_LOSS_ALPHA) || (loss->loss_fn != NTX_LOSS_MSE && loss->loss_fn != NTX_LOSS_SMAPE) ||
         (loss->alpha_loss_fn != NTX_LOSS_MSE && loss->alpha_loss_fn != NTX_LOSS_SMAPE))
         return ntx_set_error(NTX_E_INVALID, "bad ntx_loss_desc");
@@ -993,9 +1048,9 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((t->pack_total + 255) / 256)), dim3(256), 0, st, pa);
     }
     // ---- forward, every activation kept ----------------------------------------------------------------------------------------
-    const float *z = z_vals;
+    const float *z = z_vals;                                                                    // [N][S], or the S + 1 segment edges of a mip step
     if (!z) {
-        int rc = ntx_sample_depths(tnear_far, n_rays, S, flags & NTX_FLAG_PERTURB, perturb_seed, opts, t->z, stream);     // renderer.py:101-111
+        int rc = ntx_sample_depths(tnear_far, n_rays, t->ipe ? S + 1 : S, flags & NTX_FLAG_PERTURB, perturb_seed, opts, t->z, stream);     // renderer.py:101-111, 374-383
         if (rc != NTX_OK) return rc;
         z = t->z;
     }
@@ -1010,7 +1065,8 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         e.n_rays = (int)n_rays; e.S = S; e.n_geo = t->desc.n_geo; e.n_app = t->desc.n_app; e.pos_freq = t->desc.pos_freq; e.dir_freq = t->desc.dir_freq;
         e.param_freq = t->desc.param_freq; e.blur_idx = blur_idx; e.posO = t->posO; e.ptiles = t->ptiles; e.dirO = t->dirO;
         e.dtiles = t->dtiles; e.dists = t->dists;
-        hipLaunchKernelGGL(encode_kernel, dim3((unsigned)n_blocks, 2), dim3(64), 0, st, e);
+        if (t->ipe) hipLaunchKernelGGL(encode_ipe_kernel, dim3((unsigned)n_blocks, 2), dim3(64), 0, st, e);
+        else hipLaunchKernelGGL(encode_kernel, dim3((unsigned)n_blocks, 2), dim3(64), 0, st, e);
     }
     const unsigned chain_grid = (unsigned)std::min<long long>(t->cus, (n_blocks + 3) / 4);      // persistent: a workgroup of four waves per CU
     {
@@ -1019,12 +1075,13 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         f.act = t->act; f.act_stride = t->act_stride; f.bits = t->bits; f.bits_stride = t->bits_stride;
         f.sigma = t->sigma; f.raw_rgb = t->raw_rgb;
         // the direction segment of the colour layer per ray instead of per sample -- unless blur_idx scales an APPEARANCE parameter per sample
-        // (renderer.py:155-158) or a block of 32 samples can lie in two rays (S no multiple of 32)
-        const bool hoist = (blur_idx < 0 || blur_idx < t->desc.n_geo) && S % 32 == 0 && getenv("NERFTEX_TRAIN_NO_DIR_HOIST") == nullptr;
+        // (renderer.py:155-158) or a block of 32 samples can lie in two rays (S no multiple of 32).  Under the MipRenderer the parameters are
+        // per-ray constants whatever blur_idx is (the blur is the cone's radius)
+        const bool hoist = (t->ipe || blur_idx < 0 || blur_idx < t->desc.n_geo) && S % 32 == 0 && getenv("NERFTEX_TRAIN_NO_DIR_HOIST") == nullptr;
         if (hoist) {
             DirRowArgs dr{}; dr.rays_d = rays_d; dr.params = params; dr.rays_per_param_row = rays_per_param_row; dr.n_rays = (int)n_rays; dr.n_geo = t->desc.n_geo;
             dr.n_app = t->desc.n_app; dr.dir_freq = t->desc.dir_freq; dr.param_freq = t->desc.param_freq; dr.Kd = t->Kd; dr.w = t->w + t->c1.w; dr.bias = t->w + t->c1.b;
-            dr.rows = t->dirrow;
+            dr.rows = t->dirrow; dr.splice = t->ipe ? blur_idx : -1;
             hipLaunchKernelGGL(dirrow_kernel, dim3((unsigned)n_rays), dim3(256), 0, st, dr);
         }
         f.dirrow = t->dirrow; f.n_rays = (int)n_rays; f.S = S;

@@ -10,7 +10,8 @@ dicts), model, loss, schedule and renderer from the config blocks, the loop, and
 views rendered through the inference path with the trainer's weights handed over on the device, checkpoints in TensorFlow's bundle format
 with model + step + optimizer (train.py:55-57) that `Trainer.restore` resumes from.
 
-Built for the ParamNerf architecture of the shipped training configs (8 x 256, skips [4], color_depth 1; narrower widths inside it)."""
+Built for the ParamNerf architecture of the shipped training configs (8 x 256, skips [4], color_depth 1; narrower widths inside it), with
+FourierFeatures under the Renderer or -- an IntegratedPositionalEncoding model (n_pos 6) -- under the MipRenderer (renderer.py:356-473)."""
 
 from __future__ import annotations
 
@@ -26,8 +27,13 @@ class Trainer:
         """`model`: a nerf_tex_amd.model.ParamNerf container (its blob gives the initial weights); `lrate`, `lrate_decay` as train.py:49-50
         (ExponentialDecay(lrate, decay_steps=lrate_decay * 1e3, decay_rate=0.1) when lrate_decay > 0); `perturb`, `blur_idx`, `map_exr`: the
         renderer's (renderer.py:34); `raw_noise_std`: the density regulariser of map_model_output (renderer.py:190-192; config_grass_filtered_train.py:99
-        trains with 0.1), drawn per (seed, ray, sample) like the jitter."""
+        trains with 0.1), drawn per (seed, ray, sample) like the jitter.  An IPE model (pos_encoding 'ipe', n_pos 6) trains as the MipRenderer
+        renders it (renderer.py:365-444): `n_samples` cone segments between n_samples + 1 depths, the parameter rows hold the blur parameter at
+        `blur_idx` (required) -- its product with cone_scale is the cone's radius, and the model sees the other parameters."""
         import numpy as np
+        self.mip = getattr(model, "pos_encoding", "fourier") == "ipe"
+        if self.mip and blur_idx is None:
+            raise ValueError("an IPE model trains as the MipRenderer renders it, which needs blur_idx (renderer.py:385 indexes the parameters with it)")
         self.model = model
         self.device = int(device)
         self.n_samples, self.max_rays = int(n_samples), int(max_rays)
@@ -69,6 +75,7 @@ class Trainer:
             model.set_weights(weights) if isinstance(weights, (list, tuple)) else model.set_blob(weights)
         loss = util.instantiate(dict(cfg["loss_config"]))
         r = dict(cfg["renderer_config"])
+        mip = _is_mip(r)
         for k in ("module", "render_chunk", "net_chunk", "downsampling_factor"):
             r.pop(k, None)
         n_samples = int(r.pop("n_samples", 64))                                   # renderer.py:34 default
@@ -80,6 +87,10 @@ class Trainer:
             ds = cfg.get("train_dataset_config") or {}
             max_rays = int(cfg.get("batchsize", ds.get("batchsize", 1))) * int(cfg.get("rays_per_image", (ds.get("pixel_sampler_config") or {}).get("n_samples", 1024)))
         kw = dict(max_rays=max_rays, n_samples=n_samples, lrate=cfg.get("lrate", 5e-4), lrate_decay=cfg.get("lrate_decay", 0), device=device, **known)
+        if mip and n_importance > 0:
+            raise NotImplementedError("Importance sampling for mip-NeRF style rendering is not implemented in the reference either (renderer.py:403-404)")
+        if mip != (getattr(model, "pos_encoding", "fourier") == "ipe"):             # the render side's pairing (renderer.py:71, :338)
+            raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "IPE models train under MipRenderer, FourierFeatures models under Renderer")
         if n_importance > 0:                                                    # renderer.py:125-138: a coarse and a fine pass
             return CoarseFineTrainer(model, models.get(model.name + "_fine"), n_importance=n_importance, **kw), loss
         return cls(model, **kw), loss
@@ -188,7 +199,8 @@ class Trainer:
         background and counts in the loss, renderer.py:58-86), parameters [rows,P],
         cone_scale [N] or [N,1], color_true [N,3], alpha_true [N]; `loss`: a nerf_tex_amd.loss object.  Returns (loss [1], color_pred [N,3],
         alpha_pred [N]) as GPU tensors; the gradients stay in the trainer.  `z_vals` [N, n_samples]: given sample depths (`n_samples` of them,
-        default the trainer's) instead of the ones placed between t."""
+        default the trainer's) instead of the ones placed between t.  An IPE trainer (MipRenderer): parameters [rows, P + 1] with the blur parameter
+        at blur_idx, `z_vals` [N, n_samples + 1] segment edges."""
         import torch
         dev = torch.device("cuda", self.device)
         to = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32).contiguous()
@@ -391,6 +403,11 @@ class CoarseFineTrainer:
         return {"loss": val, "color_pred": c.reshape(B, R, 3), "alpha_pred": a.reshape(B, R), "color_pred_coarse": cc.reshape(B, R, 3), "alpha_pred_coarse": ac.reshape(B, R)}
 
 
+def _is_mip(renderer_config) -> bool:
+    """Whether a renderer_config block names the MipRenderer (as the reference's module path or this package's)."""
+    return str((renderer_config or {}).get("module") or "").rsplit(".", 1)[-1] == "MipRenderer"
+
+
 def _widened(model):
     """Training is built for 8 x 256.  A ParamNerf of the same shape but NARROWER (`width` < 256, even) trains inside it:
     its kernels sit in the top-left corners of the 256-wide ones (behind the encoding rows of the skip and colour layers), everything else is
@@ -455,14 +472,14 @@ def Train(target_path: str, train_dataset=None, val_dataset=None, model_config: 
     rendered every `i_img` steps.  The other arguments are the reference's: `model_config` / `loss_config` /
     `renderer_config` blocks, `n_iters`, `lrate`, `lrate_decay`, and of `logger_config` (logger.py:14) `i_print`, `i_img`, `i_checkpoint`,
     `max_to_keep`.  What the reference's Logger does at its cadences happens here: a checkpoint `checkpoints/ckpt-<step>` under `target_path`
-    (model + step + optimizer, train.py:55-57) every `i_checkpoint` steps, the validation views through `Renderer` -- the inference path, the
+    (model + step + optimizer, train.py:55-57) every `i_checkpoint` steps, the validation views through `Renderer` (`MipRenderer` for a mip run) -- the inference path, the
     trainer's weights handed over on the device -- every `i_img` steps; a run whose `target_path` holds checkpoints resumes from the newest and
     takes `n_iters - step` batches (train.py:60).  Returns {'trainer', 'renderer', 'loss' [(step, value)], 'images' {step: [RGBA [H,W,4]]},
     'checkpoints' [prefix], 'step'}."""
     import os
     import torch
     from . import checkpoint, util
-    from .renderer import Renderer
+    from .renderer import MipRenderer, Renderer
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
     if train_dataset is None:
@@ -492,7 +509,10 @@ def Train(target_path: str, train_dataset=None, val_dataset=None, model_config: 
     if rank == 0 and (logger_config or {}).get("print_model_summary", True):
         for m in ([trainer.coarse.model, trainer.fine.model] if two and not trainer.shared else [model]):      # train.py:35-36 (plot_model needs graphviz: not drawn)
             m.summary()
-    renderer = Renderer(model=model, model_fine=trainer.model_fine if two else None, **rcfg)
+    if _is_mip(cfg["renderer_config"]):                           # a mip run validates as it trains (renderer.py:356)
+        renderer = MipRenderer(model=model, **rcfg)
+    else:
+        renderer = Renderer(model=model, model_fine=trainer.model_fine if two else None, **rcfg)
     lg = dict(i_summary=10, i_print=100, i_img=5e3, i_checkpoint=1e3, max_to_keep=3, keep_every_n_hours=12)
     lg.update({k: v for k, v in (logger_config or {}).items() if k in lg})
     i_print, i_img, i_ckpt, keep, i_summary = int(lg["i_print"]), int(lg["i_img"]), int(lg["i_checkpoint"]), int(lg["max_to_keep"]), int(lg["i_summary"])

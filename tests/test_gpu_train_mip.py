@@ -1,0 +1,200 @@
+"""Training an IPE model as the MipRenderer renders it (renderer.py:356-473; `ntx_trainer_*` with NTX_POS_IPE) on the GPU, against the float64
+restatement of a mip step (tests/mip_train_restated.py, anchored to the oracle's MipRenderer in tests/test_train_mip.py).  `-m gpu`.
+
+Every layer's gradient, the loss and the predictions within 1e-4 rel-Linf of float64 autograd branched like the float32 pass; the step's
+predictions and depths against MipRenderer's; the training loop end to end with validation through MipRenderer and a bit-exact resume."""
+
+import numpy as np
+import pytest
+
+from oracle import nerftex_oracle as orc
+from tests import mip_train_restated as mtr
+from tests.common import make_model
+from tests.test_train_mip import mip_batch
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+F = np.float32
+BKGD = (1., .5, .25)
+
+
+def dev():
+    return torch.device("cuda", 0)
+
+
+def rel_linf(got, want):
+    return float(np.max(np.abs(np.asarray(got, np.float64) - want)) / max(np.max(np.abs(want)), 1e-300))
+
+
+def make_loss(name):
+    from nerf_tex_amd import loss as L
+    if name == "alpha_smape":
+        return dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse"), L.AlphaLoss(loss_fn="network.loss.smape", alpha_loss_fn="network.loss.mse")
+    return dict(kind="nerf", loss_fn="mse"), L.NerfLoss(loss_fn="network.loss.mse")
+
+
+def layer_slices(spec):
+    out, p = [], 0
+    for name, i, o in orc.layer_table(spec):
+        out.append((name + ".kernel", slice(p, p + i * o))); p += i * o
+        out.append((name + ".bias", slice(p, p + o))); p += o
+    return out
+
+
+def targets(n, seed):
+    rng = np.random.default_rng(seed)
+    color = rng.uniform(0, 1, size=(n, 3)).astype(F)
+    alpha = (rng.uniform(0, 1, size=n) > 0.3).astype(F) * rng.uniform(0.5, 1, size=n).astype(F)
+    return color, alpha
+
+
+def check_mip_step(n, S, blur_idx, perturb, loss_name, noise_std=0.0, miss=(), bkgd=False, seed=11, chunk_rays=None):
+    from nerf_tex_amd.train import Trainer
+    model, spec, wts = make_model((1, 3), kind="IPE", dense_media=True)
+    ro, rd, t, cone, params = mip_batch(n, 5, seed=3)
+    color, alpha = targets(n, 4)
+    missed = np.zeros(n, bool); missed[list(miss)] = True
+    t = t.copy(); t[missed] = np.inf
+    cone = cone.copy(); cone[missed] = np.nan                                     # whatever a ray sampler leaves there
+    okw, loss = make_loss(loss_name)
+    tr = Trainer(model, max_rays=n, n_samples=S, perturb=perturb, blur_idx=blur_idx, raw_noise_std=noise_std)
+    assert tr.n_weights == model.n_weight_floats()
+    val, cp, ap = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss, composite_bkgd=bkgd, bkgd_color=BKGD, seed=seed)
+    torch.cuda.synchronize()
+    cp, ap = cp.cpu().numpy(), ap.cpu().numpy()
+    M = n * S
+    # the S + 1 edges the step placed itself (ntx_sample_depths, renderer.py:374-383), restated
+    tf = np.where(np.isfinite(t), t, 0).astype(F)
+    z = orc.z_values_perturbed(tf, S + 1, seed, F) if perturb else orc.z_values(tf, S + 1, F)
+    z = z.copy(); z[missed] = np.inf
+    noise = noise_std * orc.noise_normals(n, S, seed, dtype=F).astype(np.float64) if noise_std > 0 else None
+    masks = [tr.activation(k, M) > 0 for k in list(range(8)) + [8, 9]]
+    sigma_mask = ((tr.activation(10, M).reshape(n, S) + (0 if noise is None else noise.astype(F))) > 0).astype(np.float64)
+    want_val, wc, wa, wg = mtr.step_gradients(wts, spec, ro, rd, z, params, np.nan_to_num(cone), color, alpha, okw, blur_idx, masks=masks,
+                                              sigma_mask=sigma_mask, noise=noise, composite_bkgd=bkgd, bkgd=BKGD, chunk_rays=chunk_rays)
+    assert abs(float(val.item()) - want_val) <= 1e-4 * abs(want_val) + 1e-7, (float(val.item()), want_val)
+    assert orc.rel_linf(np.concatenate([cp, ap[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4
+    got, flat = tr.gradients(), np.concatenate([g.ravel() for g in wg])
+    assert np.isfinite(got).all() and np.abs(flat).max() > 1e-6
+    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
+    assert max(worst.values()) <= 1e-4, {k: v for k, v in worst.items() if v > 1e-5}
+    if missed.any():                                                              # 0 / the background, and nothing comes back from them
+        assert (ap[missed] == 0).all() and (cp[missed] == (np.asarray(BKGD, F) if bkgd else 0)).all()
+        adj = tr.activation(30, M).reshape(n, S, 4)
+        assert (adj[missed] == 0).all() and np.abs(adj[~missed]).max() > 0
+    return tr
+
+
+@pytest.mark.parametrize("perturb", [False, True])
+@pytest.mark.parametrize("blur_idx", [0, 2])
+def test_mip_gradients_match_float64_autograd(perturb, blur_idx):
+    """IPE [1, 3] (pos_map 69 features, dir_map 54) at 256 rays x 64 segments: every layer's kernel and bias gradient, the loss and the
+    predictions; the blur parameter first and in the middle of the row."""
+    check_mip_step(256, 64, blur_idx, perturb, "alpha_smape")
+
+
+def test_mip_gradients_with_noise_nerf_loss_and_missing_rays():
+    """raw_noise_std 0.1, NerfLoss(mse) over a background, and rays that miss the proxy (t = inf, cone_scale NaN): they predict exactly the
+    background with zero rows of the composite's adjoint, as the reference's filter-and-scatter makes them (renderer.py:58-86)."""
+    check_mip_step(256, 64, 2, True, "nerf_mse", noise_std=0.1, miss=(0, 5, 17, 31, 32, 33, 200, 255), bkgd=True)
+
+
+@pytest.mark.parametrize("n,S,blur_idx", [(1024, 256, 0), (1021, 255, 2)])
+def test_mip_gradients_at_the_configs_batch(n, S, blur_idx):
+    """config_grass_filtered_train.py's batch (4 x 256 rays x 256 samples; perturb, raw_noise_std 0.1) with an IPE model, and a ragged
+    1021 x 255 (the per-sample direction segment: S no multiple of 32)."""
+    check_mip_step(n, S, blur_idx, True, "alpha_smape", noise_std=0.1, chunk_rays=64)
+
+
+def test_mip_step_matches_the_mip_renderer():
+    """The same weights and seed give the step's predictions and MipRenderer(...)(..., seed=s)'s, and the step's own depths are
+    ntx_sample_depths(S + 1)'s (a step handed those as z_vals is bit-identical).  After training, the MipRenderer renders the trained weights
+    handed over on the device as it renders them through the host."""
+    from nerf_tex_amd.renderer import MipRenderer
+    from nerf_tex_amd.train import Trainer
+    model, spec, wts = make_model((1, 3), kind="IPE", dense_media=True)
+    twin, _, _ = make_model((1, 3), kind="IPE", seed=9)
+    n, S, blur, seed = 512, 64, 2, 23
+    ro, rd, t, cone, params = mip_batch(n, 5, seed=5)
+    row = params[:1]
+    color, alpha = targets(n, 6)
+    okw, loss = make_loss("alpha_smape")
+    tr = Trainer(model, max_rays=n, n_samples=S, perturb=True, blur_idx=blur, raw_noise_std=0.1)
+    val, cp, ap = tr.gradients_step(ro, rd, t, row, cone, color, alpha, loss, seed=seed, rays_per_param_row=n)
+    d = lambda x: torch.as_tensor(x, device=dev())
+    view = dict(rays_o=d(ro)[None], rays_d=d(rd)[None], t=d(t)[None], parameters=d(row), cone_scale=d(cone).reshape(1, -1, 1))
+    r = MipRenderer(model=model, n_samples=S, perturb=True, blur_idx=blur, raw_noise_std=0.1)
+    out = r(**view, seed=seed)
+    got = torch.cat([cp, ap[:, None]], -1).cpu().numpy()
+    want = torch.cat([out["color_pred"][0], out["alpha_pred"][0][:, None]], -1).cpu().numpy()
+    assert want[:, 3].max() > 0.05 and orc.rel_linf(got, want) <= 1e-5
+    z = MipRenderer.sample_depths(d(t), S + 1, perturb=True, seed=seed)
+    g0 = tr.gradients()
+    val2, cp2, ap2 = tr.gradients_step(ro, rd, t, row, cone, color, alpha, loss, seed=seed, rays_per_param_row=n, z_vals=z)
+    assert float(val2.item()) == float(val.item()) and torch.equal(cp2, cp) and torch.equal(ap2, ap) and np.array_equal(tr.gradients(), g0)
+    for _ in range(3):
+        tr.step(ro, rd, t, row, cone, color, alpha, loss)
+    rt = MipRenderer(model=twin, n_samples=S, perturb=False, blur_idx=blur)
+    twin.set_weights_from_trainer(tr)
+    on_device = rt(**view, training=False)
+    twin.set_blob(tr.weights())
+    through_host = rt(**view, training=False)
+    for k in ("color_pred", "alpha_pred"):
+        assert torch.equal(on_device[k], through_host[k]) and on_device[k].abs().max() > 0
+
+
+def test_train_loop_with_the_mip_renderer(tmp_path):
+    """network.train.Train with a MipRenderer renderer_config over an in-memory dataset rendered by a teacher IPE network: the returned
+    renderer is a MipRenderer, the loss falls, the validation images are finite; a run checkpointed and resumed halfway ends bit-identical to
+    an uninterrupted one (weights, Adam's moments, iteration count)."""
+    from nerf_tex_amd import synthetic
+    from nerf_tex_amd.renderer import MipRenderer
+    from nerf_tex_amd.train import Train
+    teacher, _, _ = make_model((1, 3), kind="IPE", seed=1, dense_media=True)
+    student, _, _ = make_model((1, 3), kind="IPE", seed=0)
+    B, R, S, blur = 2, 128, 32, 0
+    ro, rd, t, cone, _ = mip_batch(B * R, 5, seed=7)
+    per_image = np.asarray([[.6, .3, .2, -.707, .707], [1.2, .1, .4, .707, .707]], F)
+    d = lambda x: torch.as_tensor(x, device=dev())
+    view = dict(rays_o=d(ro).reshape(B, R, 3), rays_d=d(rd).reshape(B, R, 3), t=d(t).reshape(B, R, 2), cone_scale=d(cone).reshape(B, R, 1), parameters=d(per_image))
+    target = MipRenderer(model=teacher, n_samples=S, perturb=False, blur_idx=blur)(**view, training=False)
+    data = dict(view, color=target["color_pred"], alpha=target["alpha_pred"])
+    assert data["alpha"].max() > 0.05
+
+    class Batches:
+        composite_bkgd, bkgd_color = False, (1., 1., 1.)
+        def __iter__(self):
+            while True:
+                yield data
+
+    class Views:
+        height, width, composite_bkgd, bkgd_color = 16, 16, False, (1., 1., 1.)
+        def __iter__(self):
+            f = synthetic.FAMILIES["grass_filtered"]
+            vo, vd, vt, vc = synthetic.all_hit_rays(16 * 16, f["b_0"], f["b_1"], f["cam"], seed=3)
+            yield dict(rays_o=d(vo)[None], rays_d=d(vd)[None], t=d(vt)[None], cone_scale=d(vc).reshape(1, -1, 1), parameters=d(per_image[:1]), seed=77)
+
+    ipe = {"module": "network.layer.IntegratedPositionalEncoding", "n_freq_bands": 10}
+    emb = lambda k: {"module": "network.model.FourierFeatures", "n_freq_bands": k}
+    common = dict(model_config={"module": "network.model.ParamNerf", "pos_embedding": ipe, "dir_embedding": emb(4), "param_embedding": emb(4),
+                                "n_parameters": [1, 3], "n_pos": 6},
+                  loss_config={"module": "network.loss.AlphaLoss", "loss_fn": "network.loss.smape", "alpha_loss_fn": "network.loss.mse"},
+                  lrate=5e-4, lrate_decay=500, weights=student.get_blob(),
+                  renderer_config={"module": "network.renderer.MipRenderer", "n_samples": S, "perturb": True, "raw_noise_std": 0.1, "blur_idx": blur})
+    lg = dict(i_print=5, i_img=30, i_checkpoint=30, max_to_keep=2, print_model_summary=False, i_summary=0)
+    out = Train(str(tmp_path / "a"), Batches(), Views(), n_iters=60, logger_config=lg, **common)
+    assert isinstance(out["renderer"], MipRenderer) and out["step"] == 60
+    losses = [v for _, v in out["loss"]]
+    assert np.isfinite(losses).all() and losses[-1] < 0.8 * losses[0] and np.mean(losses[-3:]) < np.mean(losses[:3]), losses
+    assert sorted(out["images"]) == [30, 60]
+    for step in (30, 60):
+        im = out["images"][step][0]
+        assert im.shape == (16, 16, 4) and torch.isfinite(im).all()
+    half = Train(str(tmp_path / "b"), Batches(), None, n_iters=30, logger_config=lg, **common)
+    assert half["step"] == 30
+    rest = Train(str(tmp_path / "b"), Batches(), None, n_iters=60, logger_config=lg, **common)
+    a, b = out["trainer"], rest["trainer"]
+    assert rest["step"] == 60 and a.iterations == b.iterations == 60
+    assert np.array_equal(a.weights(), b.weights())
+    for x, y in zip(a.adam_state(), b.adam_state()):
+        assert np.array_equal(x, y)
