@@ -590,19 +590,26 @@ def cone_segment_gaussians(rays_o, rays_d, t_vals, radii, dtype=F32):
 
 
 def mip_render_rays(weights, spec, rays_o, rays_d, t, parameters, cone_scale, n_samples, blur_idx, composite_bkgd,
-                    bkgd_color, map_exr=False, net_chunk=65536, z_override=None, dtype=F32):
+                    bkgd_color, map_exr=False, net_chunk=65536, z_override=None, dtype=F32, points_dtype=None):
     """MipRenderer.render_rays + map_model_output (renderer.py:365-473), perturb=False.  `parameters` [n, P+1]
-    still holds the blur parameter at `blur_idx`; the model (`spec`, an IPE ParamNerf) sees the other P."""
-    rays_o = np.asarray(rays_o, dtype=dtype); rays_d = np.asarray(rays_d, dtype=dtype)
-    t = np.asarray(t, dtype=dtype); parameters = np.asarray(parameters, dtype=dtype)
-    cone_scale = np.asarray(cone_scale, dtype=dtype).reshape(rays_o.shape[0], 1)
+    still holds the blur parameter at `blur_idx`; the model (`spec`, an IPE ParamNerf) sees the other P.
+
+    `points_dtype` (default = `dtype`): as in render_rays, the precision of the elementwise ray arithmetic in front of the
+    network -- rays_d_n, the S + 1 depths (:374-376), the cone radius (:385) and the cone-segment gaussians (:390, :411-437).
+    `dtype=float64, points_dtype=float32` is the exact network and composite on the (mean, covariance) rows a float32 run
+    evaluates."""
+    pd = dtype if points_dtype is None else points_dtype
+    rays_o = np.asarray(rays_o, dtype=pd); rays_d = np.asarray(rays_d, dtype=pd)
+    t = np.asarray(t, dtype=pd); parameters = np.asarray(parameters, dtype=pd)
+    cone_scale = np.asarray(cone_scale, dtype=pd).reshape(rays_o.shape[0], 1)
     rays_d_n = rays_d / np.sqrt(np.sum(rays_d * rays_d, -1, keepdims=True))
-    z_vals = z_values(t, n_samples + 1, dtype) if z_override is None else np.asarray(z_override, dtype=dtype)   # :374-376
+    z_vals = z_values(t, n_samples + 1, pd) if z_override is None else np.asarray(z_override, dtype=pd)       # :374-376
     blur = parameters[..., blur_idx, None] * cone_scale                                                       # :385
     params = np.concatenate([parameters[..., :blur_idx], parameters[..., blur_idx + 1:]], axis=-1)          # :386
-    mean, cov = cone_segment_gaussians(rays_o, rays_d, z_vals, blur, dtype)
+    mean, cov = cone_segment_gaussians(rays_o, rays_d, z_vals, blur, pd)
     pts = np.concatenate([mean, cov], axis=-1)                                                                # :390
     color, alpha = evaluate_model(weights, spec, pts, rays_d_n, params, None, None, None, net_chunk, dtype)
+    z_vals = np.asarray(z_vals, dtype=dtype); rays_d = np.asarray(rays_d, dtype=dtype)
     dists = (z_vals[..., 1:] - z_vals[..., :-1]) * np.sqrt(np.sum(rays_d[..., None, :] ** 2, -1))            # :441-444
     with np.errstate(over="ignore"):
         cm = (np.where(color > 0, color, np.exp(np.minimum(color, dtype(0))) - dtype(1)) + dtype(1)) if map_exr \
@@ -630,9 +637,10 @@ def mip_instance_cov(rays_d, t_vals, radii, dists, dtype=F32):
 def mip_instance_evaluate_model(weights, spec, rays_d_map, pts, t, dists, color_last, alpha_last, alpha_weight, hit,
                                 params_map, cone_scale, blur_idx, patch_scale=1.0, density_scale=1.0,
                                 density_reweighting=True, map_exr=False, composite_bkgd=False, bkgd_color=(1., 1., 1.),
-                                dtype=F32):
+                                dtype=F32, noise=None):
     """MipInstanceRenderer.evaluate_model (renderer.py:485-568): the InstanceRenderer tail with the model fed
-    (sample point, cone covariance) and the blur parameter spliced out."""
+    (sample point, cone covariance) and the blur parameter spliced out.  `noise` [n_rays,S] like dists: raw_noise_std * N(0,1)
+    added to the scaled density, as in instance_evaluate_model."""
     n_rays, S = dists.shape
     f = lambda a: np.asarray(a, dtype=dtype)
     rays_d_map, pts, t, dists, params_map = f(rays_d_map), f(pts), f(t), f(dists), f(params_map)
@@ -655,7 +663,7 @@ def mip_instance_evaluate_model(weights, spec, rays_d_map, pts, t, dists, color_
         color[sel] = c; alpha[sel] = a
     alpha = alpha.reshape(pts.shape[:-1]) * (alpha_weight if density_reweighting else dtype(1)) * dtype(density_scale)
     cm, am = instance_map_model_output(color.reshape(pts.shape), color_last, alpha, alpha_last, dists, patch_scale,
-                                       composite_bkgd, bkgd_color, map_exr, False, dtype)
+                                       composite_bkgd, bkgd_color, map_exr, False, dtype, None if noise is None else g(noise))
     color_map = np.zeros((n_rays, 3), dtype); alpha_map = np.zeros((n_rays,), dtype)
     color_map[idxs] = cm; alpha_map[idxs] = am
     return color_map, alpha_map

@@ -125,7 +125,7 @@ def test_instance_renderer(npar, blur, S, opts, precision):
     assert float(want_a.max()) > 0.3
 
 
-def _render_instanced_raw(model, bufs, hit, cone, S, precision="float32", blur=-1):
+def _render_instanced_raw(model, bufs, hit, cone, S, precision="float32", blur=-1, patch_scale=0.09, density_scale=400.0):
     from nerf_tex_amd import _lib
     rays_d_map, pts, tt, dists, color_last, alpha_last, alpha_weight, instance_id, idxs, params_map = bufs
     n = dists.shape[0]
@@ -138,7 +138,7 @@ def _render_instanced_raw(model, bufs, hit, cone, S, precision="float32", blur=-
     _lib.check(_lib.lib.ntx_render_instanced(
         model.ctx(0), t_["rd"].data_ptr(), t_["pts"].data_ptr(), t_["t"].data_ptr(), t_["dists"].data_ptr(), t_["cl"].data_ptr(),
         t_["al"].data_ptr(), t_["aw"].data_ptr(), t_["iid"].data_ptr(), t_["hit"].data_ptr(), t_["pm"].data_ptr(), t_["cone"].data_ptr(),
-        n, S, blur, 0.09, 400.0, _lib.PRECISIONS[precision], _lib.f3([1, 1, 1.]), None, None, col.data_ptr(), alp.data_ptr(), None,
+        n, S, blur, patch_scale, density_scale, _lib.PRECISIONS[precision], _lib.f3([1, 1, 1.]), None, None, col.data_ptr(), alp.data_ptr(), None,
         torch.cuda.current_stream(dv).cuda_stream))
     torch.cuda.synchronize()
     return np.concatenate([col.cpu().numpy(), alp.cpu().numpy()[:, None]], -1)

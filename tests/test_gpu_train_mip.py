@@ -86,10 +86,11 @@ def check_mip_step(n, S, blur_idx, perturb, loss_name, noise_std=0.0, miss=(), b
 
 
 @pytest.mark.parametrize("perturb", [False, True])
-@pytest.mark.parametrize("blur_idx", [0, 2])
+@pytest.mark.parametrize("blur_idx", [0, 1, 2, 4])
 def test_mip_gradients_match_float64_autograd(perturb, blur_idx):
     """IPE [1, 3] (pos_map 69 features, dir_map 54) at 256 rays x 64 segments: every layer's kernel and bias gradient, the loss and the
-    predictions; the blur parameter first and in the middle of the row."""
+    predictions; the blur parameter at every kind of slot dirrow_kernel and encode_ipe_kernel splice it from: first, in place of the
+    first appearance parameter, in the middle of the row and last."""
     check_mip_step(256, 64, blur_idx, perturb, "alpha_smape")
 
 
