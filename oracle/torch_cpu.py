@@ -10,6 +10,7 @@ nerftex_oracle.py in tests/test_oracle.py.  Every function cites the file:line o
 
 from __future__ import annotations
 
+import math
 from typing import List, Sequence
 
 import numpy as np
@@ -25,34 +26,82 @@ def fourier_features(x: torch.Tensor, n_freq: int) -> torch.Tensor:
     return torch.cat(out, -1)
 
 
-def model_forward(w: Sequence[torch.Tensor], spec, pos, dirs, params):
-    """ParamNerf / Nerf (model.py:58-125 / 9-45); `w` in Keras get_weights() order (nerftex_oracle.layer_table)."""
+def ipe(mean, cov, n_freq):
+    """layer.py:31-41 on [M, 3] means and covariances: [sin(y) e^(-y_var/2) | sin(y + pi/2) e^(-y_var/2)], y = 2^f x_c at index 3 f + c."""
+    freq = torch.as_tensor(2.0 ** np.arange(n_freq), dtype=mean.dtype)
+    y = (mean[:, None, :] * freq[:, None]).reshape(-1, 3 * n_freq)
+    y_var = (cov[:, None, :] * freq[:, None] ** 2).reshape(-1, 3 * n_freq)
+    return torch.sin(torch.cat([y, y + 0.5 * math.pi], -1)) * torch.exp(-0.5 * torch.cat([y_var, y_var], -1))
+
+
+def cone_segment_gaussians(rays_o, rays_d, z, radii):
+    """renderer.py:411-437: z [n, S+1] edges, radii [n, 1] -> mean [n, S, 3], diagonal covariance [n, S, 3]."""
+    t0, t1 = z[:, :-1], z[:, 1:]
+    mu, hw = (t0 + t1) / 2, (t1 - t0) / 2
+    den = 3 * mu ** 2 + hw ** 2
+    t_mean = mu + (2 * mu * hw ** 2) / den
+    t_var = hw ** 2 / 3 - (4 / 15) * ((hw ** 4 * (12 * mu ** 2 - hw ** 2)) / den ** 2)
+    r_var = radii ** 2 * (mu ** 2 / 4 + (5 / 12) * hw ** 2 - 4 / 15 * hw ** 4 / den)
+    mean = rays_o[:, None, :] + rays_d[:, None, :] * t_mean[..., None]
+    d_mag_sq = torch.clamp(torch.sum(rays_d ** 2, -1, keepdim=True), min=1e-10)
+    null = 1 - rays_d ** 2 / d_mag_sq
+    cov = t_var[..., None] * (rays_d ** 2)[:, None, :] + r_var[..., None] * null[:, None, :]
+    return mean, cov
+
+
+def mlp(w: Sequence[torch.Tensor], spec, pos_map, dirs, params, masks=None):
+    """ParamNerf / Nerf (model.py:58-125 / 9-45) behind the position encoding: `pos_map` is FourierFeatures(pos) or IPE(mean, cov), the
+    geometry parameters' features are appended here; `w` in Keras get_weights() order (nerftex_oracle.layer_table).
+    `masks` None: the network's own ReLUs.  Otherwise every ReLU is replaced by a GIVEN 0/1 pattern, in the order trunk 0..depth-1,
+    colour layers, colour half: the network as a float32 forward pass branched it.  A pre-activation within float32 rounding of zero
+    falls on either side of its ReLU depending on summation order; autograd through the masked network follows the pattern it is handed
+    instead of float64's own."""
     g, a = spec.n_geo, spec.n_app
-    pos_map = fourier_features(pos, spec.pos_freq)                                    # model.py:77
     dir_map = fourier_features(dirs, spec.dir_freq)                                   # model.py:78
     if g > 0:
         pos_map = torch.cat([pos_map, fourier_features(params[:, :g], spec.param_freq)], -1)       # :88-93
     if a > 0:
         dir_map = torch.cat([dir_map, fourier_features(params[:, g:g + a], spec.param_freq)], -1)  # :96-101
+    mk = None if masks is None else iter(masks)
+    act = torch.relu if mk is None else (lambda x: x * next(mk))
     it = iter(range(0, len(w) - 2, 2))
+
+    def dense(h):
+        j = next(it)
+        return torch.addmm(w[j + 1], h, w[j])
+
     h = pos_map
     for i in range(spec.depth):                                                       # :104-108
-        j = next(it)
-        h = torch.relu(torch.addmm(w[j + 1], h, w[j]))
+        h = act(dense(h))
         if i in spec.skips:
             h = torch.cat([pos_map, h], -1)
     alpha = torch.addmm(w[-1], h, w[-2])                                              # :111 (last in get_weights())
-    j = next(it)
-    h = torch.addmm(w[j + 1], h, w[j])                                                # :114
-    h = torch.cat([dir_map, h], -1)                                                   # :115
+    h = torch.cat([dir_map, dense(h)], -1)                                            # :114-115: the feature layer has no activation
     if spec.kind == "ParamNerf":
         for _ in range(spec.color_depth):                                             # :118-119
-            j = next(it)
-            h = torch.relu(torch.addmm(w[j + 1], h, w[j]))
-    j = next(it)
-    h = torch.relu(torch.addmm(w[j + 1], h, w[j]))                                    # :122
-    j = next(it)
-    return torch.addmm(w[j + 1], h, w[j]), alpha                                      # :123
+            h = act(dense(h))
+    h = act(dense(h))                                                                 # :122
+    return dense(h), alpha                                                            # :123
+
+
+def model_forward(w: Sequence[torch.Tensor], spec, pos, dirs, params):
+    """The network on sample positions: FourierFeatures(pos) (model.py:77) into `mlp`."""
+    return mlp(w, spec, fourier_features(pos, spec.pos_freq), dirs, params)
+
+
+def composite(color, alpha, dists, map_exr=False, composite_bkgd=False, bkgd=(1., 1., 1.), sigma_mask=None, noise=None):
+    """map_model_output (renderer.py:170-213 / 439-473) on raw network outputs color [n, S, 3], alpha [n, S] and the samples' lengths
+    `dists` [n, S] (the two renderers differ in these alone).  `sigma_mask`: a GIVEN 0/1 pattern in place of the density's ReLU, as `mlp`'s."""
+    if noise is not None:                                                             # :190-192: [n, S], raw_noise_std * N(0,1)
+        alpha = alpha + noise
+    rgb = torch.nn.functional.elu(color) + 1 if map_exr else torch.sigmoid(color)     # :187
+    am = 1. - torch.exp(-(torch.relu(alpha) if sigma_mask is None else alpha * sigma_mask) * dists)   # :195
+    trans = torch.cumprod(1. - am + 1e-10, -1)
+    wts = am * torch.cat([torch.ones_like(trans[:, :1]), trans[:, :-1]], -1)          # :198 exclusive cumprod
+    c = torch.sum(wts[..., None] * rgb, -2); a = torch.sum(wts, -1)                   # :201, 207
+    if composite_bkgd:
+        c = c + (1. - a[..., None]) * torch.as_tensor(bkgd, dtype=c.dtype)
+    return c, a
 
 
 def render_rays(w, spec, rays_o, rays_d, t, parameters, cone_scale, n_samples: int, blur_idx=None, net_chunk: int = 65536):
@@ -75,11 +124,7 @@ def render_rays(w, spec, rays_o, rays_d, t, parameters, cone_scale, n_samples: i
     color = torch.cat(color, 0).reshape(n, n_samples, 3); alpha = torch.cat(alpha, 0).reshape(n, n_samples)
     dists = z[:, 1:] - z[:, :-1]                                                      # :174
     dists = torch.cat([dists, dists[:, -1:]], -1) * torch.linalg.norm(rays_d, dim=-1, keepdim=True)   # :177, 180
-    rgb = torch.sigmoid(color)                                                        # :187
-    am = 1. - torch.exp(-torch.relu(alpha) * dists)                                   # :195
-    trans = torch.cumprod(1. - am + 1e-10, -1)
-    wts = am * torch.cat([torch.ones_like(trans[:, :1]), trans[:, :-1]], -1)          # :198 exclusive cumprod
-    return torch.sum(wts[..., None] * rgb, -2), torch.sum(wts, -1)                    # :201, 207
+    return composite(color, alpha, dists)
 
 
 def renderer_call(w_np: List[np.ndarray], spec, rays_o, rays_d, t, parameters_row, cone_scale, n_samples: int, blur_idx=None,

@@ -1,5 +1,5 @@
-"""One training step of the reference restated on the CPU: network/train.py:61-67 over network/renderer.py:92-213 and network/loss.py:6-59,
-with torch autograd in FLOAT64 standing in for tf.GradientTape, and TF 2.4's Adam + ExponentialDecay (train.py:49-52) written out.
+"""One training step of the reference restated on the CPU: network/train.py:61-67 over network/renderer.py:92-213 (Renderer) or :356-473 (MipRenderer) and
+network/loss.py:6-59, with torch autograd in FLOAT64 standing in for tf.GradientTape, and TF 2.4's Adam + ExponentialDecay (train.py:49-52) written out.
 
 TEST INFRASTRUCTURE ONLY (the rules of nerftex_oracle.py: nothing under nerf_tex_amd/ imports it).  PARITY UNPINNED: TensorFlow cannot
 run here and the reference ships no gradients; the forward pass is torch_cpu.py's (checked against nerftex_oracle.py in
@@ -39,115 +39,121 @@ def alpha_loss(color_true, alpha_true, color_pred, alpha_pred, loss_fn="mse", al
     return fn(color_true, color_pred) + gamma * afn(alpha_true, alpha_pred)
 
 
-def model_forward_masked(w, spec, pos, dirs, params, masks):
-    """torch_cpu.model_forward with every ReLU replaced by a GIVEN 0/1 pattern (`masks`: trunk 0..depth-1, then the colour layers): the
-    network as a float32 forward pass branched it.  A pre-activation within float32 rounding of zero falls on either side of its ReLU
-    depending on summation order; autograd through this function follows the pattern it is handed instead of float64's own."""
-    ff = torch_cpu.fourier_features
-    g, a = spec.n_geo, spec.n_app
-    pos_map = ff(pos, spec.pos_freq); dir_map = ff(dirs, spec.dir_freq)
-    if g > 0:
-        pos_map = torch.cat([pos_map, ff(params[:, :g], spec.param_freq)], -1)
-    if a > 0:
-        dir_map = torch.cat([dir_map, ff(params[:, g:g + a], spec.param_freq)], -1)
-    it = iter(range(0, len(w) - 2, 2)); mk = iter(masks)
-    h = pos_map
-    for i in range(spec.depth):
-        j = next(it)
-        h = torch.addmm(w[j + 1], h, w[j]) * next(mk)
-        if i in spec.skips:
-            h = torch.cat([pos_map, h], -1)
-    alpha = torch.addmm(w[-1], h, w[-2])
-    j = next(it)
-    h = torch.cat([dir_map, torch.addmm(w[j + 1], h, w[j])], -1)
-    for _ in range(spec.color_depth):
-        j = next(it)
-        h = torch.addmm(w[j + 1], h, w[j]) * next(mk)
-    j = next(it)
-    h = torch.addmm(w[j + 1], h, w[j]) * next(mk)
-    j = next(it)
-    return torch.addmm(w[j + 1], h, w[j]), alpha
+composite = torch_cpu.composite
+
+
+def fourier_dists(z, rays_d):
+    """renderer.py:174-180: a sample reaches to the next one, the last as far as the one before it; times |d|."""
+    dists = z[:, 1:] - z[:, :-1]
+    return torch.cat([dists, dists[:, -1:]], -1) * torch.linalg.norm(rays_d, dim=-1, keepdim=True)
+
+
+def mip_dists(z, rays_d):
+    """renderer.py:441-444: the S segments between the S + 1 edges; times |d|."""
+    return (z[:, 1:] - z[:, :-1]) * torch.linalg.norm(rays_d, dim=-1, keepdim=True)
 
 
 def render(w, spec, rays_o, rays_d, z, parameters, cone_scale, blur_idx=None, map_exr=False, composite_bkgd=False, bkgd=(1., 1., 1.), masks=None,
            sigma_mask=None, noise=None):
-    """Renderer.render_rays on given sample depths z [n, S] (renderer.py:114-213; the depths themselves, :101-111, are the caller's:
-    with perturb they come from the product's restated generator, nerftex_oracle.sample_depths)."""
-    n, S = z.shape
+    """render_rays on GIVEN depths (the depths themselves, renderer.py:101-111 / 374-383, are the caller's: with perturb they come from the
+    product's restated generator, nerftex_oracle.sample_depths), by the model's position encoding:
+    "fourier": Renderer.render_rays (renderer.py:114-213) on sample depths z [n, S];
+    "ipe": MipRenderer.render_rays (:365-409) + map_model_output (:439-473) on segment edges z [n, S + 1]; parameters [n, P + 1] hold the blur
+    parameter at `blur_idx`, the model sees the other P.
+    `masks` / `sigma_mask`: torch_cpu.mlp's and torch_cpu.composite's."""
+    n = z.shape[0]
     rays_d_n = rays_d / torch.linalg.norm(rays_d, dim=-1, keepdim=True)
-    pts = rays_o[:, None, :] + rays_d[:, None, :] * z[:, :, None]
-    pos = pts.reshape(-1, 3)
-    dirs = rays_d_n.repeat_interleave(S, 0)
-    params = parameters.repeat_interleave(S, 0)
-    if blur_idx is not None:
-        scale = (cone_scale.reshape(n, 1, 1) * z[:, :, None]).reshape(-1, 1)
-        params = torch.cat([params[:, :blur_idx], params[:, blur_idx, None] * scale, params[:, blur_idx + 1:]], -1)
-    if masks is None:
-        color, alpha = torch_cpu.model_forward(w, spec, pos, dirs, params)
+    if spec.pos_encoding == "ipe":
+        if blur_idx is None:
+            raise ValueError("an IPE model is rendered by the MipRenderer, which needs blur_idx")
+        S = z.shape[1] - 1
+        blur = parameters[:, blur_idx, None] * cone_scale.reshape(n, 1)
+        params = torch.cat([parameters[:, :blur_idx], parameters[:, blur_idx + 1:]], -1).repeat_interleave(S, 0)
+        mean, cov = torch_cpu.cone_segment_gaussians(rays_o, rays_d, z, blur)
+        pos_map = torch_cpu.ipe(mean.reshape(-1, 3), cov.reshape(-1, 3), spec.pos_freq)
+        dists = mip_dists(z, rays_d)
     else:
-        color, alpha = model_forward_masked(w, spec, pos, dirs, params, masks)
-    color = color.reshape(n, S, 3); alpha = alpha.reshape(n, S)
-    return composite(color, alpha, z, rays_d, map_exr, composite_bkgd, bkgd, sigma_mask, noise)
+        S = z.shape[1]
+        pts = rays_o[:, None, :] + rays_d[:, None, :] * z[:, :, None]
+        params = parameters.repeat_interleave(S, 0)
+        if blur_idx is not None:
+            scale = (cone_scale.reshape(n, 1, 1) * z[:, :, None]).reshape(-1, 1)
+            params = torch.cat([params[:, :blur_idx], params[:, blur_idx, None] * scale, params[:, blur_idx + 1:]], -1)
+        pos_map = torch_cpu.fourier_features(pts.reshape(-1, 3), spec.pos_freq)
+        dists = fourier_dists(z, rays_d)
+    color, alpha = torch_cpu.mlp(w, spec, pos_map, rays_d_n.repeat_interleave(S, 0), params, masks)
+    return composite(color.reshape(n, S, 3), alpha.reshape(n, S), dists, map_exr, composite_bkgd, bkgd, sigma_mask, noise)
 
 
-def composite(color, alpha, z, rays_d, map_exr=False, composite_bkgd=False, bkgd=(1., 1., 1.), sigma_mask=None, noise=None):
-    """map_model_output (renderer.py:170-213) on raw network outputs color [n, S, 3], alpha [n, S]."""
-    if noise is not None:                                                                   # renderer.py:190-192: [n, S], raw_noise_std * N(0,1)
-        alpha = alpha + noise
-    dists = z[:, 1:] - z[:, :-1]
-    dists = torch.cat([dists, dists[:, -1:]], -1) * torch.linalg.norm(rays_d, dim=-1, keepdim=True)
-    rgb = torch.nn.functional.elu(color) + 1 if map_exr else torch.sigmoid(color)
-    am = 1. - torch.exp(-(torch.relu(alpha) if sigma_mask is None else alpha * sigma_mask) * dists)
-    trans = torch.cumprod(1. - am + 1e-10, -1)
-    wts = am * torch.cat([torch.ones_like(trans[:, :1]), trans[:, :-1]], -1)
-    c = torch.sum(wts[..., None] * rgb, -2); a = torch.sum(wts, -1)
-    if composite_bkgd:
-        c = c + (1. - a[..., None]) * torch.as_tensor(bkgd, dtype=c.dtype)
-    return c, a
+def _loss(loss, color_true, alpha_true, c, a):
+    kw = {k: v for k, v in loss.items() if k != "kind"}
+    return nerf_loss(color_true, c, **kw) if loss["kind"] == "nerf" else alpha_loss(color_true, alpha_true, c, a, **kw)
 
 
 def composite_gradients(raw_rgb, sigma, z, rays_d, color_true, alpha_true, loss, map_exr=False, composite_bkgd=False, bkgd=(1., 1., 1.), noise=None,
                         dtype=torch.float64):
-    """The composite and the loss alone under autograd: (loss, color_pred, alpha_pred, dL/d raw_rgb [n, S, 3], dL/d sigma [n, S]) for GIVEN raw
+    """The Renderer's composite and the loss alone under autograd: (loss, color_pred, alpha_pred, dL/d raw_rgb [n, S, 3], dL/d sigma [n, S]) for GIVEN raw
     network outputs -- what a hand-written adjoint of renderer.py:170-213 + loss.py is compared with, apart from the network's own rounding."""
     t_ = lambda a: None if a is None else torch.tensor(np.asarray(a), dtype=dtype)
     rgb = torch.tensor(np.asarray(raw_rgb), dtype=dtype, requires_grad=True); sg = torch.tensor(np.asarray(sigma), dtype=dtype, requires_grad=True)
-    c, a = composite(rgb, sg, t_(z), t_(rays_d), map_exr, composite_bkgd, bkgd, None, t_(noise))
-    kw = {k: v for k, v in loss.items() if k != "kind"}
-    val = nerf_loss(t_(color_true), c, **kw) if loss["kind"] == "nerf" else alpha_loss(t_(color_true), t_(alpha_true), c, a, **kw)
+    c, a = composite(rgb, sg, fourier_dists(t_(z), t_(rays_d)), map_exr, composite_bkgd, bkgd, None, t_(noise))
+    val = _loss(loss, t_(color_true), t_(alpha_true), c, a)
     val.backward()
     return float(val.detach()), c.detach().numpy(), a.detach().numpy(), rgb.grad.numpy(), sg.grad.numpy()
 
 
 def step_gradients(w_np, spec, rays_o, rays_d, z, parameters, cone_scale, color_true, alpha_true, loss, blur_idx=None, map_exr=False,
-                   composite_bkgd=False, bkgd=(1., 1., 1.), dtype=torch.float64, masks=None, sigma_mask=None, noise=None):
+                   composite_bkgd=False, bkgd=(1., 1., 1.), dtype=torch.float64, masks=None, sigma_mask=None, noise=None, chunk_rays=None, workers=1):
     """(loss, color_pred, alpha_pred, gradients in get_weights() order as a list of arrays) of one step; `loss` = dict(kind='nerf'|'alpha', **kwargs).
-    `masks` / `sigma_mask`: the ReLU patterns of a float32 forward pass (model_forward_masked), as 0/1 arrays; `noise` [n, S]: the density
-    regulariser's draws (raw_noise_std * N(0,1), renderer.py:190-192)."""
-    w = [torch.tensor(np.asarray(a), dtype=dtype, requires_grad=True) for a in w_np]
+    Renderer.__call__ (renderer.py:58-86): rays whose depths are not finite (t = inf: they miss the proxy) are filtered out, the rest
+    rendered, the results scattered back into zeros -- plus the background colour for the filtered ones when compositing -- and the loss runs
+    over ALL rays.
+    `masks` [M, width] per ReLU layer / `sigma_mask` [n, S]: the ReLU patterns of a float32 forward pass (torch_cpu.mlp), 0/1 or bool; `noise`
+    [n, S]: the density regulariser's draws (raw_noise_std * N(0,1), renderer.py:190-192).
+    `chunk_rays`: for a batch too large for one autograd pass in float64 (the configs' 1024 rays x 256 samples).  The losses of loss.py are
+    MEANS over the rays, so the batch's loss and gradient are the ray-count-weighted sums of its chunks' -- evaluated `chunk_rays` rays at a
+    time (bounded memory, minutes of CPU; `workers` chunks at once on Python threads: the matrices of a chunk are too small to keep every
+    BLAS thread busy; the masks reach the working dtype a chunk at a time: 67 MB each as bool at that batch, 537 MB in float64), added up
+    in chunk order."""
+    z = np.asarray(z)
+    n, S = z.shape[0], z.shape[1] - (spec.pos_encoding == "ipe")
+    hit_all = np.isfinite(z).all(1)
     t_ = lambda a: None if a is None else torch.tensor(np.asarray(a), dtype=dtype)
-    mk = None if masks is None else [t_(m) for m in masks]
-    hit = np.isfinite(np.asarray(z)[:, 0])
-    if hit.all():
-        c, a = render(w, spec, t_(rays_o), t_(rays_d), t_(z), t_(parameters), t_(cone_scale), blur_idx, map_exr, composite_bkgd, bkgd, mk,
-                      None if sigma_mask is None else t_(sigma_mask), t_(noise))
-    else:
-        # Renderer.__call__ (renderer.py:58-86): rays whose t is inf are filtered out, the rest rendered, the results scattered back into zeros --
-        # plus the background colour for the filtered ones when compositing -- and the loss runs over ALL rays
-        S = np.asarray(z).shape[1]
-        rows = np.repeat(hit, S)
-        sub = lambda x: None if x is None else t_(np.asarray(x)[hit])
-        ch, ah = render(w, spec, sub(rays_o), sub(rays_d), sub(z), sub(parameters), sub(cone_scale), blur_idx, map_exr, composite_bkgd, bkgd,
-                        None if mk is None else [m[torch.as_tensor(rows)] for m in mk], sub(sigma_mask), sub(noise))
-        idx = torch.as_tensor(np.nonzero(hit)[0])
-        c = torch.zeros((hit.size, 3), dtype=dtype).index_put((idx,), ch)
-        a = torch.zeros((hit.size,), dtype=dtype).index_put((idx,), ah)
+
+    def one(r0):
+        r1 = min(n, r0 + (chunk_rays or n))
+        hit = hit_all[r0:r1]
+        sub = lambda x: None if x is None else t_(np.asarray(x)[r0:r1][hit])
+        mk = None if masks is None else [sub(m.reshape(n, S, -1)).flatten(0, 1) for m in map(np.asarray, masks)]
+        w = [torch.tensor(np.asarray(a), dtype=dtype, requires_grad=True) for a in w_np]
+        c = torch.zeros((r1 - r0, 3), dtype=dtype); a = torch.zeros((r1 - r0,), dtype=dtype)
+        if hit.any():
+            ch, ah = render(w, spec, sub(rays_o), sub(rays_d), sub(z), sub(parameters), sub(cone_scale), blur_idx, map_exr, composite_bkgd, bkgd, mk,
+                            sub(sigma_mask), sub(noise))
+            idx = torch.as_tensor(np.nonzero(hit)[0])
+            c = c.index_put((idx,), ch); a = a.index_put((idx,), ah)
         if composite_bkgd:
             c = c + torch.as_tensor((~hit)[:, None] * np.asarray(bkgd, np.float64)[None, :], dtype=dtype)
-    kw = {k: v for k, v in loss.items() if k != "kind"}
-    val = nerf_loss(t_(color_true), c, **kw) if loss["kind"] == "nerf" else alpha_loss(t_(color_true), t_(alpha_true), c, a, **kw)
-    val.backward()
-    return float(val.detach()), c.detach().numpy(), a.detach().numpy(), [x.grad.numpy() for x in w]
+        val = _loss(loss, t_(np.asarray(color_true)[r0:r1]), None if alpha_true is None else t_(np.asarray(alpha_true)[r0:r1]), c, a)
+        if val.requires_grad:
+            val.backward()
+        return (r1 - r0) / n, float(val.detach()), c.detach().numpy(), a.detach().numpy(), [np.zeros(x.shape) if x.grad is None else x.grad.numpy() for x in w]
+
+    starts = list(range(0, n, chunk_rays or n))
+    if len(starts) == 1:
+        return one(0)[1:]
+    if workers > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(workers) as ex:
+            parts = list(ex.map(one, starts))
+    else:
+        parts = map(one, starts)
+    total, grads, cs, al = 0.0, None, [], []
+    for wgt, val, c, a, g in parts:                                                      # in chunk order, whatever order they finished in
+        total += val * wgt
+        grads = [x * wgt for x in g] if grads is None else [acc + x * wgt for acc, x in zip(grads, g)]
+        cs.append(c); al.append(a)
+    return total, np.concatenate(cs), np.concatenate(al), grads
 
 
 def adam_step(w, g, m, v, iterations, lrate, decay_steps=0.0, decay_rate=0.1, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dtype=np.float64):
@@ -167,42 +173,12 @@ def adam_step(w, g, m, v, iterations, lrate, decay_steps=0.0, decay_rate=0.1, be
 
 def step_gradients_chunked(w_np, spec, rays_o, rays_d, z, parameters, cone_scale, color_true, alpha_true, loss, chunk_rays=16, masks=None, sigma_mask=None,
                            noise=None, workers=None, **kw):
-    """`step_gradients` on a batch too large for one autograd pass in float64 (the configs' 1024 rays x 256 samples): the losses of loss.py
-    are MEANS over the rays, so the batch's loss and gradient are the ray-count-weighted sums of its chunks' -- evaluated `chunk_rays` rays at
-    a time (bounded memory, minutes of CPU; `workers` chunks at once on Python threads: the matrices of a chunk are too small to keep every
-    BLAS thread busy), added up in chunk order.  Every ray must hit (the filter-and-scatter branch of step_gradients is per call).
-    `masks`: [M, width] arrays (bool is fine), `sigma_mask` / `noise`: [n, S]."""
+    """`step_gradients` 16 rays at a time on NTX_ORACLE_WORKERS threads (default 4): what bench.py's parity block calls."""
     import os
-    from concurrent.futures import ThreadPoolExecutor
     if workers is None:
         workers = int(os.environ.get("NTX_ORACLE_WORKERS", "4"))
-    z = np.asarray(z)
-    n, S = z.shape
-    assert np.isfinite(z).all(), "chunked evaluation is for all-hit batches"
-
-    def one(r0):
-        r1 = min(n, r0 + chunk_rays)
-        sl, rows = slice(r0, r1), slice(r0 * S, r1 * S)
-        val, c, a, g = step_gradients(w_np, spec, np.asarray(rays_o)[sl], np.asarray(rays_d)[sl], z[sl], np.asarray(parameters)[sl],
-                                      None if cone_scale is None else np.asarray(cone_scale)[sl], np.asarray(color_true)[sl],
-                                      None if alpha_true is None else np.asarray(alpha_true)[sl], loss,
-                                      masks=None if masks is None else [np.asarray(m[rows], np.float64) for m in masks],
-                                      sigma_mask=None if sigma_mask is None else np.asarray(sigma_mask[sl], np.float64),
-                                      noise=None if noise is None else np.asarray(noise)[sl], **kw)
-        return (r1 - r0) / n, val, c, a, g
-
-    starts = list(range(0, n, chunk_rays))
-    if workers > 1 and len(starts) > 1:
-        with ThreadPoolExecutor(workers) as ex:
-            parts = list(ex.map(one, starts))
-    else:
-        parts = [one(r0) for r0 in starts]
-    total, grads, cs, al = 0.0, None, [], []
-    for wgt, val, c, a, g in parts:                                                      # in chunk order, whatever order they finished in
-        total += val * wgt
-        grads = [x * wgt for x in g] if grads is None else [acc + x * wgt for acc, x in zip(grads, g)]
-        cs.append(c); al.append(a)
-    return total, np.concatenate(cs), np.concatenate(al), grads
+    return step_gradients(w_np, spec, rays_o, rays_d, z, parameters, cone_scale, color_true, alpha_true, loss, masks=masks, sigma_mask=sigma_mask, noise=noise,
+                          chunk_rays=chunk_rays, workers=workers, **kw)
 
 
 def step_gradients_coarse_fine(w_coarse_np, w_fine_np, spec, rays_o, rays_d, z_coarse, z_fine, parameters, cone_scale, color_true, alpha_true, loss,
@@ -218,9 +194,7 @@ def step_gradients_coarse_fine(w_coarse_np, w_fine_np, spec, rays_o, rays_d, z_c
     args = (t_(rays_o), t_(rays_d))
     c1, a1 = render(wc, spec, *args, t_(z_coarse), t_(parameters), t_(cone_scale), masks=mk(masks_coarse), sigma_mask=t_(sigma_mask_coarse), noise=t_(noise_coarse), **kw)
     c2, a2 = render(wf, spec, *args, t_(z_fine), t_(parameters), t_(cone_scale), masks=mk(masks_fine), sigma_mask=t_(sigma_mask_fine), noise=t_(noise_fine), **kw)
-    lk = {k: v for k, v in loss.items() if k != "kind"}
-    one = (lambda c, a: nerf_loss(t_(color_true), c, **lk)) if loss["kind"] == "nerf" else (lambda c, a: alpha_loss(t_(color_true), t_(alpha_true), c, a, **lk))
-    val = one(c2, a2) + one(c1, a1)
+    val = _loss(loss, t_(color_true), t_(alpha_true), c2, a2) + _loss(loss, t_(color_true), t_(alpha_true), c1, a1)
     val.backward()
     g = lambda w: [x.grad.numpy() for x in w]
     return float(val.detach()), (c2.detach().numpy(), a2.detach().numpy()), (c1.detach().numpy(), a1.detach().numpy()), g(wc), None if w_fine_np is None else g(wf)

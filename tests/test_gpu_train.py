@@ -13,6 +13,7 @@ import pytest
 from oracle import nerftex_oracle as orc
 from oracle import train_oracle as tro
 from tests.common import make_model
+from tests.train_common import LOSSES, layer_slices, make_loss, rel_linf, restated_step, step_pred                  # (tests/_dp_train_worker.py and tools/dev/ take them from here)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -21,10 +22,6 @@ F = np.float32
 
 def dev():
     return torch.device("cuda", 0)
-
-
-def rel_linf(got, want):
-    return float(np.max(np.abs(np.asarray(got, np.float64) - want)) / max(np.max(np.abs(want)), 1e-300))
 
 
 @pytest.mark.parametrize("ak,bk,M,N,K", [(1, 0, 300, 200, 77), (1, 0, 257, 129, 256), (0, 0, 337, 256, 1000), (1, 0, 128, 128, 32), (0, 0, 72, 3, 5000), (1, 0, 4096, 256, 128),
@@ -63,25 +60,6 @@ def batch(seed, n, S, P, fam):
     return ro, rd, t, cone, params, color, alpha
 
 
-LOSSES = {"alpha_smape": (dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse"), dict(loss_fn="network.loss.smape", alpha_loss_fn="network.loss.mse")),
-          "alpha_mse_soft": (dict(kind="alpha", loss_fn="mse", gamma=0.5, use_hard_mask=False), dict(loss_fn="network.loss.mse", gamma=0.5, use_hard_mask=False)),
-          "nerf_mse": (dict(kind="nerf", loss_fn="mse"), dict(loss_fn="network.loss.mse"))}
-
-
-def make_loss(name):
-    from nerf_tex_amd import loss as L
-    okw, pkw = LOSSES[name]
-    return okw, (L.AlphaLoss(**pkw) if okw["kind"] == "alpha" else L.NerfLoss(**pkw))
-
-
-def layer_slices(spec):
-    out, p = [], 0
-    for name, i, o in orc.layer_table(spec):
-        out.append((name + ".kernel", slice(p, p + i * o))); p += i * o
-        out.append((name + ".bias", slice(p, p + o))); p += o
-    return out
-
-
 @pytest.mark.parametrize("fam,npar,blur,loss_name,bkgd", [("carpet", (1, 6), None, "alpha_smape", False), ("grass", (1, 4), None, "nerf_mse", True),
                                                          ("grass_filtered", (2, 3), 0, "alpha_mse_soft", False)])
 @pytest.mark.parametrize("perturb", [False, True])
@@ -110,12 +88,10 @@ def test_shipped_training_configs_run_as_written(fam):
     ro, rd, t, cone, params, color, alpha = batch(2, n, S, P, fam if fam != "plush" else "grass")
     wts = orc.split_blob(spec, tr.weights())
     val, cp, ap = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss, seed=5)
-    z = orc.z_values_perturbed(t, S, 5, np.float32)
-    noise = tr.raw_noise_std * orc.noise_normals(n, S, 5, dtype=np.float32).astype(np.float64) if tr.raw_noise_std > 0 else None
-    want_val, wc, wa, _ = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse"),
-                                              blur_idx=tr.blur_idx, noise=noise)
-    assert orc.rel_linf(np.concatenate([cp.cpu().numpy(), ap.cpu().numpy()[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4
-    assert abs(float(val.item()) - want_val) <= 1e-4 * abs(want_val)
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse"), seed=5, perturb=True,
+                         noise_std=tr.raw_noise_std, blur_idx=tr.blur_idx, free=True)
+    assert orc.rel_linf(step_pred(cp, ap), want.pred) <= 1e-4
+    assert abs(float(val.item()) - want.loss) <= 1e-4 * abs(want.loss)
     g = tr.gradients()
     assert np.isfinite(g).all() and np.abs(g).max() > 1e-6
     tr.apply_gradients()
@@ -140,21 +116,11 @@ def test_rays_that_miss_the_proxy_stay_in_the_batch(bkgd):
     torch.cuda.synchronize()
     cp, ap = cp.cpu().numpy(), ap.cpu().numpy()
     assert (ap[miss] == 0).all() and (cp[miss] == (np.asarray([1., .5, .25], np.float32) if bkgd else 0)).all()
-    M = n * S
-    z = orc.z_values_perturbed(np.where(np.isfinite(t), t, 0).astype(np.float32), S, 11, np.float32)
-    z[miss] = np.inf
-    noise = 0.1 * orc.noise_normals(n, S, 11, dtype=np.float32).astype(np.float64)
-    masks = [(tr.activation(k, M) > 0).astype(np.float64) for k in list(range(8)) + [8, 9]]
-    sigma_mask = ((tr.activation(10, M).reshape(n, S) + noise.astype(np.float32)) > 0).astype(np.float64)
-    want_val, wc, wa, wg = tro.step_gradients(wts, spec, ro, rd, z, params, np.nan_to_num(cone), color, alpha, okw, masks=masks, sigma_mask=sigma_mask, blur_idx=0,
-                                              composite_bkgd=bkgd, bkgd=(1., .5, .25), noise=noise)
-    assert abs(float(val.item()) - want_val) <= 1e-5 * abs(want_val) + 1e-7
-    assert orc.rel_linf(np.concatenate([cp, ap[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4
-    got, flat = tr.gradients(), np.concatenate([g.ravel() for g in wg])
-    assert np.isfinite(got).all() and np.abs(flat).max() > 1e-6
-    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
-    assert max(worst.values()) <= 1e-4, {k: v for k, v in worst.items() if v > 1e-5}
-
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=11, perturb=True, noise_std=0.1, miss=miss, blur_idx=0, bkgd=bkgd)
+    assert abs(float(val.item()) - want.loss) <= 1e-5 * abs(want.loss) + 1e-7
+    assert orc.rel_linf(np.concatenate([cp, ap[:, None]], -1), want.pred) <= 1e-4
+    assert np.isfinite(want.got).all() and np.abs(want.grad).max() > 1e-6
+    assert max(want.layers.values()) <= 1e-4, {k: v for k, v in want.layers.items() if v > 1e-5}
 
 def test_train_step_takes_the_reference_batch_dict():
     """`Trainer.train_step(data, ...)` on the dict network/dataset.py hands train.py:61 -- [B, R, ...] tensors, one parameter row per image --
@@ -211,36 +177,24 @@ def check_gradients(fam, npar, blur, loss_name, bkgd, perturb, n, S, floor_check
     ro, rd, t, cone, params, color, alpha = batch(3, n, S, P, fam)
     okw, loss = make_loss(loss_name)
     tr = Trainer(model, max_rays=n, n_samples=S, perturb=perturb, blur_idx=blur, raw_noise_std=raw_noise_std)
-    # the sample depths the kernel places itself (renderer.py:101-111; with perturb: the product's Philox jitter), restated for the oracle
-    z = orc.z_values_perturbed(t, S, 11, np.float32) if perturb else orc.z_values(t, S, np.float32)
     val, cp, ap = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss, composite_bkgd=bkgd, bkgd_color=(1., .5, .25), seed=11)
-    torch.cuda.synchronize()
-    got = tr.gradients()
-    # float64 autograd, branched like the float32 forward pass was: the signs of the activations the step kept (a pre-activation within
-    # rounding of zero falls on either side of its ReLU depending on summation order -- in TensorFlow's float32 as much as here)
-    M = n * S
-    masks = [(tr.activation(k, M) > 0).astype(np.float64) for k in list(range(8)) + [8, 9]]
-    # the density regulariser (renderer.py:190-192): the product's restated draws, keyed like the jitter by (seed, ray, sample)
-    noise = raw_noise_std * orc.noise_normals(n, S, 11, dtype=np.float32).astype(np.float64) if raw_noise_std > 0 else None
-    sigma_mask = ((tr.activation(10, M).reshape(n, S) + (0 if noise is None else noise.astype(np.float32))) > 0).astype(np.float64)
-    kw = dict(blur_idx=blur, composite_bkgd=bkgd, bkgd=(1., .5, .25), noise=noise)
-    want_val, wc, wa, wg = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, masks=masks, sigma_mask=sigma_mask, **kw)
+    step = (tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw)
+    kw = dict(seed=11, perturb=perturb, noise_std=raw_noise_std, blur_idx=blur, bkgd=bkgd)
+    want = restated_step(*step, **kw)
     # (a handful of rays with a handful of coarse steps each: 1 - exp(-sigma dist) at dist ~ 0.5 carries a float32 sigma's rounding five times as
     # far, and nothing averages out -- those cases are here for the kernels' granules, at five times the tolerance)
     tiny = 5.0 if n * S < 100 else 1.0
-    assert abs(float(val.item()) - want_val) <= (1e-5 if n * S >= 1000 else 1e-4) * tiny * abs(want_val) + 1e-7
-    assert orc.rel_linf(np.concatenate([cp.cpu().numpy(), ap.cpu().numpy()[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4 * tiny
-    flat = np.concatenate([g.ravel() for g in wg])
-    assert flat.size == got.size == tr.n_weights
-    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
-    assert max(worst.values()) <= 1e-4 * tiny, {k: v for k, v in worst.items() if v > 1e-5}
-    assert np.abs(flat).max() > 1e-6 or n * S < 100                              # a gradient worth the name (a handful of samples may see none)
+    assert abs(float(val.item()) - want.loss) <= (1e-5 if n * S >= 1000 else 1e-4) * tiny * abs(want.loss) + 1e-7
+    assert orc.rel_linf(step_pred(cp, ap), want.pred) <= 1e-4 * tiny
+    got = want.got
+    assert max(want.layers.values()) <= 1e-4 * tiny, {k: v for k, v in want.layers.items() if v > 1e-5}
+    assert np.abs(want.grad).max() > 1e-6 or n * S < 100                         # a gradient worth the name (a handful of samples may see none)
     if not floor_check:
         return
     # ... and against float64 autograd left to its own branches: as close as float32 autograd of the same restatement gets (the float32 floor
     # of this comparison, measured beside it), and the two patterns differ in a handful of units
-    free = np.concatenate([g.ravel() for g in tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, **kw)[3]])
-    f32 = np.concatenate([g.ravel() for g in tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, dtype=torch.float32, **kw)[3]])
+    free = restated_step(*step, free=True, **kw).grad
+    f32 = restated_step(*step, free=True, dtype=torch.float32, **kw).grad
     for name, sl in layer_slices(spec):
         floor = rel_linf(f32[sl], free[sl])
         assert rel_linf(got[sl], free[sl]) <= max(1e-4, 4 * floor), (name, rel_linf(got[sl], free[sl]), floor)
@@ -258,25 +212,17 @@ def step_errors(model, spec, wts, fam, n, S, loss_name, perturb=False, bkgd=Fals
     okw, loss = make_loss(loss_name)
     tr = Trainer(model, max_rays=cap or n, n_samples=S, perturb=perturb, blur_idx=blur, raw_noise_std=noise_std)
     val, cp, ap_ = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss, composite_bkgd=bkgd, bkgd_color=(1., .5, .25), seed=seed)
-    torch.cuda.synchronize()
+    kw = dict(seed=seed, perturb=perturb, noise_std=noise_std, miss=miss, blur_idx=blur, bkgd=bkgd)
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, **kw)
+    got, flat, z, noise, want_val, want_pred = want.got, want.grad, want.z, want.noise, want.loss, want.pred
     M = n * S
-    tf = np.where(np.isfinite(t), t, 0).astype(np.float32)
-    z = orc.z_values_perturbed(tf, S, seed, np.float32) if perturb else orc.z_values(tf, S, np.float32)
-    z = z.copy(); z[miss] = np.inf
-    noise = noise_std * orc.noise_normals(n, S, seed, dtype=np.float32).astype(np.float64) if noise_std > 0 else None
-    masks = [(tr.activation(k, M) > 0).astype(np.float64) for k in list(range(8)) + [8, 9]]
     sg = tr.activation(10, M).reshape(n, S)
-    sigma_mask = ((sg + (0 if noise is None else noise.astype(np.float32))) > 0).astype(np.float64)
-    kw = dict(masks=masks, sigma_mask=sigma_mask, blur_idx=blur, composite_bkgd=bkgd, bkgd=(1., .5, .25), noise=noise)
-    want_val, wc, wa, wg = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, **kw)
-    got, flat = tr.gradients(), np.concatenate([g.ravel() for g in wg])
     gmax = float(np.abs(flat).max())
     lerr = lambda sl: float(np.abs(got[sl] - flat[sl]).max() / max(float(np.abs(flat[sl]).max()), 1e-6 * gmax, 1e-30))
-    want_pred = np.concatenate([wc, wa[:, None]], -1)
     out = dict(e_loss=abs(float(val.item()) - want_val) / (abs(want_val) + 1e-7),
-               e_pred=orc.rel_linf(np.concatenate([cp.cpu().numpy(), ap_.cpu().numpy()[:, None]], -1), want_pred),
+               e_pred=orc.rel_linf(step_pred(cp, ap_), want_pred),
                layers={nm: lerr(sl) for nm, sl in layer_slices(spec)} if gmax > 0 else {"all": float(np.abs(got).max())},
-               finite=bool(np.isfinite(got).all()), got=got, want=flat, gmax=gmax, alpha_pred=wa, sigma=sg, z=z)
+               finite=bool(np.isfinite(got).all()), got=got, want=flat, gmax=gmax, alpha_pred=want_pred[:, 3], sigma=sg, z=z)
     out["e_grad"] = max(out["layers"].values())
     # the composite's adjoint on its own: dL/d raw colour, dL/d raw density as the step left them against float64 autograd of the composite and
     # the loss on the step's OWN float32 network outputs (the network's rounding, which exp(-sigma dist) amplifies by sigma dist, stays out)
@@ -292,10 +238,9 @@ def step_errors(model, spec, wts, fam, n, S, loss_name, perturb=False, bkgd=Fals
         out["e_drgb"] = rel_linf(dg[hit][..., :3], d_rgb * scale) if np.abs(d_rgb).max() > 0 else float(np.abs(dg[hit][..., :3]).max())
         out["dsigma_max"] = float(np.abs(d_sg).max() * scale)
     if floors:
-        _, fc, fa, fg = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, dtype=torch.float32, **kw)
-        f32 = np.concatenate([g.ravel() for g in fg])
-        out["floor_pred"] = orc.rel_linf(np.concatenate([fc, fa[:, None]], -1), want_pred)
-        out["floors"] = {nm: rel_linf(f32[sl], flat[sl]) for nm, sl in layer_slices(spec)}
+        f = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, dtype=torch.float32, **kw)
+        out["floor_pred"] = orc.rel_linf(f.pred, want_pred)
+        out["floors"] = {nm: rel_linf(f.grad[sl], flat[sl]) for nm, sl in layer_slices(spec)}
     return out
 
 
@@ -491,29 +436,18 @@ def test_gradients_at_the_configs_batch(fam, npar, blur, noise_std, n, S):
     8192 blocks of 32 samples over 1024 persistent waves, every workgroup of the weight gradients with its share of every layer, each
     family on its own build of the forward chain -- and a ragged neighbour.  Every layer's gradient, the loss and the predictions against
     float64 autograd, which takes the batch 16 rays at a time, four chunks at once (the loss is a mean over rays: oracle/train_oracle.py
-    step_gradients_chunked; 9 s a case on the GPU box's host, 26 s one chunk at a time), branched by the signs of the activations the step kept."""
+    step_gradients with chunk_rays; 9 s a case on the GPU box's host, 26 s one chunk at a time), branched by the signs of the activations the step kept."""
     from nerf_tex_amd.train import Trainer
     model, spec, wts = make_model(npar, dense_media=True)
     ro, rd, t, cone, params, color, alpha = batch(21, n, S, sum(npar), fam)
     okw, loss = make_loss("alpha_smape")
     tr = Trainer(model, max_rays=n, n_samples=S, perturb=True, blur_idx=blur, raw_noise_std=noise_std)
     val, cp, ap = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss, seed=4)
-    torch.cuda.synchronize()
-    got = tr.gradients()
-    M = n * S
-    masks = [tr.activation(k, M) > 0 for k in list(range(8)) + [8, 9]]                   # bool: 67 MB each
-    noise = noise_std * orc.noise_normals(n, S, 4, dtype=np.float32).astype(np.float64) if noise_std > 0 else None
-    sigma_mask = (tr.activation(10, M).reshape(n, S) + (0 if noise is None else noise.astype(np.float32))) > 0
-    z = orc.z_values_perturbed(t, S, 4, np.float32)
-    want_val, wc, wa, wg = tro.step_gradients_chunked(wts, spec, ro, rd, z, params, cone, color, alpha, okw, chunk_rays=16, masks=masks, sigma_mask=sigma_mask,
-                                                      noise=noise, blur_idx=blur)
-    assert abs(float(val.item()) - want_val) <= 1e-5 * abs(want_val)
-    assert orc.rel_linf(np.concatenate([cp.cpu().numpy(), ap.cpu().numpy()[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4
-    flat = np.concatenate([g.ravel() for g in wg])
-    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
-    assert max(worst.values()) <= 1e-4, {k: v for k, v in worst.items() if v > 1e-5}
-    assert np.abs(flat).max() > 1e-6
-
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=4, perturb=True, noise_std=noise_std, blur_idx=blur, chunk_rays=16, workers=4)
+    assert abs(float(val.item()) - want.loss) <= 1e-5 * abs(want.loss)
+    assert orc.rel_linf(step_pred(cp, ap), want.pred) <= 1e-4
+    assert max(want.layers.values()) <= 1e-4, {k: v for k, v in want.layers.items() if v > 1e-5}
+    assert np.abs(want.grad).max() > 1e-6
 
 @pytest.mark.parametrize("npar,freqs", [((0, 3), None), ((1, 2), (4, 2, 2)), ((3, 0), (6, 4, 3))])
 def test_gradients_with_narrow_encodings(npar, freqs):
@@ -527,17 +461,9 @@ def test_gradients_with_narrow_encodings(npar, freqs):
     okw, loss = make_loss("alpha_smape")
     tr = Trainer(model, max_rays=n, n_samples=S, perturb=False)
     val, cp, ap = tr.gradients_step(ro, rd, t, params if P else None, cone, color, alpha, loss)
-    torch.cuda.synchronize()
-    M = n * S
-    masks = [(tr.activation(k, M) > 0).astype(np.float64) for k in list(range(8)) + [8, 9]]
-    sigma_mask = (tr.activation(10, M).reshape(n, S) > 0).astype(np.float64)
-    z = orc.z_values(t, S, np.float32)
-    want_val, wc, wa, wg = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, masks=masks, sigma_mask=sigma_mask)
-    assert abs(float(val.item()) - want_val) <= 1e-5 * abs(want_val)
-    got, flat = tr.gradients(), np.concatenate([g.ravel() for g in wg])
-    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
-    assert max(worst.values()) <= 1e-4, {k: v for k, v in worst.items() if v > 1e-5}
-
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=0, perturb=False)
+    assert abs(float(val.item()) - want.loss) <= 1e-5 * abs(want.loss)
+    assert max(want.layers.values()) <= 1e-4, {k: v for k, v in want.layers.items() if v > 1e-5}
 
 @pytest.mark.parametrize("width", [128, 64, 30])
 def test_a_narrower_network_trains_inside_the_256_wide_one(width):
@@ -555,18 +481,11 @@ def test_a_narrower_network_trains_inside_the_256_wide_one(width):
     tr = Trainer(model, max_rays=n, n_samples=S, perturb=False)
     assert tr.n_weights == model.n_weight_floats() < tr._n_native and np.array_equal(tr.weights(), np.asarray(model.get_blob(), np.float32).reshape(-1))
     val, cp, ap = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss)
-    torch.cuda.synchronize()
-    M = n * S
-    masks = [(tr.activation(k, M) > 0).astype(np.float64) for k in list(range(8)) + [8, 9]]
-    assert [m.shape[1] for m in masks] == [width] * 9 + [width // 2]
-    sigma_mask = (tr.activation(10, M).reshape(n, S) > 0).astype(np.float64)
-    z = orc.z_values(t, S, np.float32)
-    want_val, wc, wa, wg = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, masks=masks, sigma_mask=sigma_mask)
-    assert abs(float(val.item()) - want_val) <= 1e-5 * abs(want_val)
-    assert orc.rel_linf(np.concatenate([cp.cpu().numpy(), ap.cpu().numpy()[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4
-    got, flat = tr.gradients(), np.concatenate([g.ravel() for g in wg])
-    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
-    assert max(worst.values()) <= 1e-4 and np.abs(flat).max() > 1e-6, {k: v for k, v in worst.items() if v > 1e-5}
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=0, perturb=False)
+    assert [m.shape[1] for m in want.masks] == [width] * 9 + [width // 2]
+    assert abs(float(val.item()) - want.loss) <= 1e-5 * abs(want.loss)
+    assert orc.rel_linf(step_pred(cp, ap), want.pred) <= 1e-4
+    assert max(want.layers.values()) <= 1e-4 and np.abs(want.grad).max() > 1e-6, {k: v for k, v in want.layers.items() if v > 1e-5}
     tr.apply_gradients()
     for _ in range(2):
         pred = tr.step(ro, rd, t, params, cone, color, alpha, loss)

@@ -1,5 +1,5 @@
 """Training an IPE model as the MipRenderer renders it (renderer.py:356-473; `ntx_trainer_*` with NTX_POS_IPE) on the GPU, against the float64
-restatement of a mip step (tests/mip_train_restated.py, anchored to the oracle's MipRenderer in tests/test_train_mip.py).  `-m gpu`.
+restatement of a mip step (oracle/train_oracle.py on an IPE spec, anchored to the oracle's MipRenderer in tests/test_train_mip.py).  `-m gpu`.
 
 Every layer's gradient, the loss and the predictions within 1e-4 rel-Linf of float64 autograd branched like the float32 pass; the step's
 predictions and depths against MipRenderer's; the training loop end to end with validation through MipRenderer and a bit-exact resume."""
@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 
 from oracle import nerftex_oracle as orc
-from tests import mip_train_restated as mtr
 from tests.common import make_model
-from tests.test_train_mip import mip_batch
+from tests.train_common import make_loss, mip_batch, restated_step, targets
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -20,32 +19,6 @@ BKGD = (1., .5, .25)
 
 def dev():
     return torch.device("cuda", 0)
-
-
-def rel_linf(got, want):
-    return float(np.max(np.abs(np.asarray(got, np.float64) - want)) / max(np.max(np.abs(want)), 1e-300))
-
-
-def make_loss(name):
-    from nerf_tex_amd import loss as L
-    if name == "alpha_smape":
-        return dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse"), L.AlphaLoss(loss_fn="network.loss.smape", alpha_loss_fn="network.loss.mse")
-    return dict(kind="nerf", loss_fn="mse"), L.NerfLoss(loss_fn="network.loss.mse")
-
-
-def layer_slices(spec):
-    out, p = [], 0
-    for name, i, o in orc.layer_table(spec):
-        out.append((name + ".kernel", slice(p, p + i * o))); p += i * o
-        out.append((name + ".bias", slice(p, p + o))); p += o
-    return out
-
-
-def targets(n, seed):
-    rng = np.random.default_rng(seed)
-    color = rng.uniform(0, 1, size=(n, 3)).astype(F)
-    alpha = (rng.uniform(0, 1, size=n) > 0.3).astype(F) * rng.uniform(0.5, 1, size=n).astype(F)
-    return color, alpha
 
 
 def check_mip_step(n, S, blur_idx, perturb, loss_name, noise_std=0.0, miss=(), bkgd=False, seed=11, chunk_rays=None):
@@ -60,24 +33,14 @@ def check_mip_step(n, S, blur_idx, perturb, loss_name, noise_std=0.0, miss=(), b
     tr = Trainer(model, max_rays=n, n_samples=S, perturb=perturb, blur_idx=blur_idx, raw_noise_std=noise_std)
     assert tr.n_weights == model.n_weight_floats()
     val, cp, ap = tr.gradients_step(ro, rd, t, params, cone, color, alpha, loss, composite_bkgd=bkgd, bkgd_color=BKGD, seed=seed)
-    torch.cuda.synchronize()
+    want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=seed, perturb=perturb, noise_std=noise_std, miss=missed, blur_idx=blur_idx,
+                         bkgd=bkgd, bkgd_color=BKGD, chunk_rays=chunk_rays)
     cp, ap = cp.cpu().numpy(), ap.cpu().numpy()
     M = n * S
-    # the S + 1 edges the step placed itself (ntx_sample_depths, renderer.py:374-383), restated
-    tf = np.where(np.isfinite(t), t, 0).astype(F)
-    z = orc.z_values_perturbed(tf, S + 1, seed, F) if perturb else orc.z_values(tf, S + 1, F)
-    z = z.copy(); z[missed] = np.inf
-    noise = noise_std * orc.noise_normals(n, S, seed, dtype=F).astype(np.float64) if noise_std > 0 else None
-    masks = [tr.activation(k, M) > 0 for k in list(range(8)) + [8, 9]]
-    sigma_mask = ((tr.activation(10, M).reshape(n, S) + (0 if noise is None else noise.astype(F))) > 0).astype(np.float64)
-    want_val, wc, wa, wg = mtr.step_gradients(wts, spec, ro, rd, z, params, np.nan_to_num(cone), color, alpha, okw, blur_idx, masks=masks,
-                                              sigma_mask=sigma_mask, noise=noise, composite_bkgd=bkgd, bkgd=BKGD, chunk_rays=chunk_rays)
-    assert abs(float(val.item()) - want_val) <= 1e-4 * abs(want_val) + 1e-7, (float(val.item()), want_val)
-    assert orc.rel_linf(np.concatenate([cp, ap[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)) <= 1e-4
-    got, flat = tr.gradients(), np.concatenate([g.ravel() for g in wg])
-    assert np.isfinite(got).all() and np.abs(flat).max() > 1e-6
-    worst = {name: rel_linf(got[sl], flat[sl]) for name, sl in layer_slices(spec)}
-    assert max(worst.values()) <= 1e-4, {k: v for k, v in worst.items() if v > 1e-5}
+    assert abs(float(val.item()) - want.loss) <= 1e-4 * abs(want.loss) + 1e-7, (float(val.item()), want.loss)
+    assert orc.rel_linf(np.concatenate([cp, ap[:, None]], -1), want.pred) <= 1e-4
+    assert np.isfinite(want.got).all() and np.abs(want.grad).max() > 1e-6
+    assert max(want.layers.values()) <= 1e-4, {k: v for k, v in want.layers.items() if v > 1e-5}
     if missed.any():                                                              # 0 / the background, and nothing comes back from them
         assert (ap[missed] == 0).all() and (cp[missed] == (np.asarray(BKGD, F) if bkgd else 0)).all()
         adj = tr.activation(30, M).reshape(n, S, 4)

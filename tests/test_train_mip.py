@@ -1,5 +1,5 @@
 """Training an IPE model as the MipRenderer renders it (renderer.py:356-473): the parts that need no GPU.  The float64 restatement of a mip
-step (tests/mip_train_restated.py) is anchored to the oracle's MipRenderer, and the trainer's dispatch on the renderer_config's module and
+step (oracle/train_oracle.py on an IPE spec) is anchored to the oracle's MipRenderer, and the trainer's dispatch on the renderer_config's module and
 the C ABI's acceptance of the IPE descriptor are checked before any device is asked for."""
 
 import ctypes as C
@@ -9,24 +9,16 @@ import pytest
 
 from oracle import nerftex_oracle as orc
 from tests.common import make_model
+from tests.train_common import mip_batch
 
 torch = pytest.importorskip("torch")
-
-
-def mip_batch(n, P_in, seed=0):
-    from nerf_tex_amd import synthetic
-    f = synthetic.FAMILIES["grass_filtered"]
-    ro, rd, t, cone = synthetic.all_hit_rays(n, f["b_0"], f["b_1"], f["cam"], seed=seed + 1)
-    rng = np.random.default_rng(seed)
-    params = rng.uniform(0.2, 1.5, size=(n, P_in)).astype(np.float32)
-    return ro, rd, t, cone, params
 
 
 @pytest.mark.parametrize("blur_idx", [0, 2, 4])
 def test_restated_mip_forward_matches_the_oracle(blur_idx):
     """The restatement's forward in float64 (cone-segment gaussians, IPE, the MLP, the composite with the mip dists) against
     nerftex_oracle.mip_render_rays on the same rays and depths, perturb off."""
-    from tests import mip_train_restated as mtr
+    from oracle import train_oracle as tro
     model, spec, wts = make_model((1, 3), kind="IPE", dense_media=True)
     n, S = 24, 20
     ro, rd, t, cone, params = mip_batch(n, 5)
@@ -34,7 +26,7 @@ def test_restated_mip_forward_matches_the_oracle(blur_idx):
     z = orc.z_values(np.asarray(t, np.float64), S + 1, np.float64)
     assert np.array_equal(z, want["z_vals"])
     t_ = lambda a: torch.tensor(np.asarray(a, np.float64))
-    c, a = mtr.render([t_(w) for w in wts], spec, t_(ro), t_(rd), t_(z), t_(params), t_(cone), blur_idx, composite_bkgd=True, bkgd=(1., .5, .25))
+    c, a = tro.render([t_(w) for w in wts], spec, t_(ro), t_(rd), t_(z), t_(params), t_(cone), blur_idx, composite_bkgd=True, bkgd=(1., .5, .25))
     got = np.concatenate([c.numpy(), a.numpy()[:, None]], -1)
     ref = np.concatenate([want["color_pred"], want["alpha_pred"][:, None]], -1)
     assert np.abs(ref[:, 3]).max() > 0.05                                        # media that the rays see

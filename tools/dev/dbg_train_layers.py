@@ -55,12 +55,9 @@ for i in range(7, 0, -1):
     Wi = K(f"trunk{i}", 256 + (Kp if i == 5 else 0))[-256:]
     report(f"d h{i - 1}", dy[i - 1], (dy[i] @ Wi.T) * (h[i - 1] > 0))
 # weight gradients against the oracle (branched by the kept activations)
-masks = [(tr.activation(k, M) > 0).astype(np.float64) for k in list(range(8)) + [8, 9]]
-sigma_mask = (tr.activation(10, M).reshape(n, S) > 0).astype(np.float64)
-want_val, wc, wa, wg = tro.step_gradients(wts, spec, ro, rd, z, params, cone, color, alpha, okw, masks=masks, sigma_mask=sigma_mask)
-print("loss", float(val.item()), want_val, "pred rel-Linf", orc.rel_linf(np.concatenate([cp.cpu().numpy(), ap.cpu().numpy()[:, None]], -1), np.concatenate([wc, wa[:, None]], -1)))
-got = tr.gradients(); flat = np.concatenate([g.ravel() for g in wg])
+want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=11, perturb=False)
+print("loss", float(val.item()), want.loss, "pred rel-Linf", orc.rel_linf(step_pred(cp, ap), want.pred))
 for name, s_ in layer_slices(spec):
-    print(name.ljust(24), '%.3e' % rel_linf(got[s_], flat[s_]), '%.3e' % np.abs(flat[s_]).max(), flush=True)
+    print(name.ljust(24), '%.3e' % want.layers[name], '%.3e' % np.abs(want.grad[s_]).max(), flush=True)
 # d h7 needs the oracle's d feature and d sigma: from the weight gradients above being right it follows; here its own consistency
 Wf = K("feature", 256); Wa = K("alpha", 256)[:, 0]
