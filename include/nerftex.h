@@ -201,7 +201,12 @@ int ntx_generate_rays_strided(const float *c2w, int height, int width, float foc
                               float near_t, float far_t, float *rays_o, float *rays_d, float *t, float *cone_scale,
                               ntx_stream stream);
 
-/* Replaces layer.FourierFeatures.call (layer.py:22-23): x[M,D] -> out[M, D*(1+2*n_freq)] (DEVICE). */
+/* Replaces layer.FourierFeatures.call (layer.py:22-23): x[M,D] -> out[M, D*(1+2*n_freq)] (DEVICE).  n_freq 0..30, any x: every
+ * sin / cos is within 2.5e-7 of the exact value at the float32 argument 2^k x (the library sine where |2^k x| >= 2^17); inf / NaN
+ * give NaN features of that component.
+ * The encoders FUSED into the network kernels (ntx_mlp_forward, ntx_render_rays, ntx_render_instanced, the training step) evaluate the
+ * fast sine alone, which holds its 1.5 ulp on |2^f x| < 2^17: positions |pos| < 256 at pos_freq 10.  Beyond that domain the fused
+ * features lose accuracy (6e-7 at 2^20, not a sine from 2^24 on). */
 int ntx_fourier_features(const float *x, int64_t m, int d, int n_freq, float *out, ntx_stream stream);
 
 /* Replaces model((pos, dirs, params), training) (renderer.py:161; model.py:58-125):
@@ -211,7 +216,7 @@ int ntx_mlp_forward(ntx_ctx *ctx, const float *pos, const float *dirs, const flo
 
 /* Replaces Renderer.map_model_output (renderer.py:170-213): color[N,S,3], sigma[N,S], z[N,S],
  * rays_d[N,3] -> color_out[N,3], alpha_out[N], optional weights_out[N,S] (NULL to skip).
- * bkgd: HOST float[3]. */
+ * bkgd: HOST float[3].  A NaN density makes its ray's colour and alpha NaN, as tf.nn.relu propagates it (:195). */
 int ntx_composite(const float *color, const float *sigma, const float *z_vals, const float *rays_d,
                   int64_t n_rays, int n_samples, uint32_t flags, const float *bkgd, float *color_out,
                   float *alpha_out, float *weights_out, ntx_stream stream);

@@ -74,6 +74,8 @@ NTX_DEV float sin_q(float x, int q) {
 
 NTX_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 NTX_DEV float elu1f_(float x) { return (x > 0.0f ? x : expf(x) - 1.0f) + 1.0f; }
+// tf.nn.relu of the density (renderer.py:195 / 339): a NaN stays a NaN (v_max_f32(NaN, 0) is 0), so the composite reports it
+NTX_DEV float relu_nan(float x) { return x < 0.0f ? 0.0f : x; }
 
 // ---------------------------------------------------------------------------------------------
 // weight stream: every wave reads the packed stream strictly in order, RING records ahead.
@@ -950,7 +952,7 @@ NTX_DEV void composite_step(RayAccum &ra, float sigma, const float (&raw)[3], fl
     float c[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = (flags & NTX_FLAG_MAP_EXR) ? elu1f_(raw[k]) : sigmoidf_(raw[k]);   // :182-187
-    const float a = valid ? 1.0f - expf(-__builtin_fmaxf(sigma + noise, 0.0f) * dist) : 0.0f;          // :195
+    const float a = valid ? 1.0f - expf(-relu_nan(sigma + noise) * dist) : 0.0f;          // :195
     composite_core<W>(ra, a, c, valid, j, w_out);
 }
 
@@ -1930,7 +1932,7 @@ __global__ __launch_bounds__(256) void instance_kernel(InstanceArgs a) {
         }
         if (a.flags & NTX_FLAG_RAW_NOISE)                                                         // :335-337
             sigma += a.raw_noise_std * normal01(global_index(a.idx0, a.idx_run, a.idx_stride, ray2), idx2, a.seed_lo, a.seed_hi);
-        const float al = valid2 ? 1.0f - expf(-__builtin_fmaxf(sigma, 0.0f) * dist_l / a.patch_scale) : 0.0f;   // :339
+        const float al = valid2 ? 1.0f - expf(-relu_nan(sigma) * dist_l / a.patch_scale) : 0.0f;   // :339
         const int sl0 = __builtin_amdgcn_readfirstlane(sl2);
         const bool whole = (uint32_t)__ballot(valid2 && sl2 == sl0) == 0xffffffffu;   // 32 lanes of one ray: tails are shorter
         if (whole) {

@@ -663,6 +663,8 @@ __global__ __launch_bounds__(256) void instance_kernel_x3(InstanceArgs a) {
             const int64_t ray_l = sm / S;
             sigma += a.raw_noise_std * normal01(global_index(a.idx0, a.idx_run, a.idx_stride, ray_l), (int)(sm - ray_l * S), a.seed_lo, a.seed_hi);
         }
+        // (fmaxf swallows a NaN density where ntx_device.h's relu_nan propagates it: that select costs instance_kernel_x3 of the
+        // [1,4] family a register it does not have -- 8 bytes of scratch -- so this frozen path keeps fmaxf)
         const float al = valid ? 1.0f - expf(-__builtin_fmaxf(sigma, 0.0f) * a.dists[sm] / a.patch_scale) : 0.0f;   // :339
         if (mode == 1) {
             composite_core<32>(ra, al, col, true, j, nullptr);

@@ -107,6 +107,21 @@ def test_mlp_forward(kind, npar, m):
     assert err <= 2e-5, err         # what exact-f32 MFMA should actually reach on glorot weights
 
 
+@pytest.mark.parametrize("kind,npar", FAMS)
+def test_mlp_forward_at_the_edge_of_the_encoder_domain(kind, npar):
+    """The fused encoders evaluate sin_q alone, whose domain is |2^f x| < 2^17 (include/nerftex.h: |pos| < 256 at pos_freq 10):
+    positions uniform in [-250, 250] against the float64 network on the same float32 points, at test_mlp_forward's bars."""
+    m = 4096 + 17
+    model, spec, w = make_model(npar, kind)
+    pos, dirs, params = random_samples(m, sum(npar), box=250.0)
+    assert 200 < float(np.abs(pos).max()) < 256
+    color, alpha = model(tuple(to_dev(pos, dirs, params)))
+    rc, ra = orc.model_forward(w, spec, pos, dirs, params, np.float64)
+    err = orc.rel_linf(np.concatenate([color.cpu().numpy(), alpha.cpu().numpy()], -1), np.concatenate([rc, ra], -1))
+    assert err <= TOL, err
+    assert err <= 2e-5, err
+
+
 @pytest.mark.parametrize("family,S", [("carpet", 32), ("carpet", 64), ("grass", 128), ("fur", 64), ("grass_filtered", 48)])
 @pytest.mark.parametrize("bk", [False, True])
 def test_render_rays_camera(family, S, bk):

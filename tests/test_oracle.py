@@ -420,3 +420,63 @@ def test_layer_order_follows_keras_graph_depth_rule():
     t = dict((n, (i, o)) for n, i, o in orc.layer_table(orc.ModelSpec(param_depth=2)))
     assert t["param_geo0"] == (9, 128) and t["param_geo1"] == (128, 128) and t["param_app0"] == (54, 128) and t["trunk0"] == (63 + 128, 256) \
         and t["trunk5"] == (256 + 63 + 128, 256) and t["color_hidden0"] == (256 + 27 + 128, 256)
+
+
+# --------------------------------------------------------------------------------------
+# the references of tests/test_gpu_standalone_edges.py, checked without a GPU
+# --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("weight", [0.0, 0.25, 0.013])
+@pytest.mark.parametrize("S", [66, 130])
+def test_sample_pdf_dyadic_cases_are_exact(S, weight):
+    """The exact cases of the GPU test (64 / 128 equal interior weights, depths 2 + i/32, u = k/1024): float64 orc.sample_pdf equals a
+    brute-force per-sample inverse CDF in rational arithmetic, so a wrong oracle cannot bless a wrong kernel; and the float32
+    emulation of the kernel's own arithmetic (strided sums, butterfly, Hillis-Steele scan with carry, search, interpolation) gives
+    the same values bit for bit, so the 1-ulp bar of the GPU test is one the kernel's order of operations meets."""
+    from fractions import Fraction
+    from tests import kernel_emulation as emu
+    t, z, w, u = emu.dyadic_case(S, weight)
+    z64 = z.astype(np.float64)
+    got = orc.sample_pdf(0.5 * (z64[:, 1:] + z64[:, :-1]), w.astype(np.float64)[:, 1:-1], u.shape[1], det=False, u=u.astype(np.float64), dtype=np.float64)
+    want = emu.sample_pdf_exact([Fraction(float(v)) for v in z[0]], [Fraction(float(v)) for v in w[0]], [Fraction(float(v)) for v in u[0]])
+    assert [Fraction(float(v)) for v in got[0]] == want
+    kernel = emu.sample_pdf_f32(z, w, u)
+    assert np.array_equal(kernel, got.astype(np.float32))
+    ks = set(int(round(float(v) * 1024)) for v in u[0])
+    assert {0, 1024} <= ks and all(k in ks for k in range(0, 1025, 1024 // (S - 2)))     # both outcomes of every comparison of the search
+
+
+@pytest.mark.parametrize("pattern", ["floor", "spike", "zero"])
+@pytest.mark.parametrize("S,NI", [(3, 1), (3, 7), (4, 64), (64, 64), (65, 65), (66, 64), (67, 129), (130, 200), (257, 64), (512, 512)])
+def test_sample_pdf_float32_restatement_meets_the_gpu_bound(S, NI, pattern):
+    """What tests/test_gpu_standalone_edges.py asks of ntx_sample_pdf -- every depth within `allowed` of float64, and `allowed` below
+    0.1 coarse bin for 90 % of the samples -- is met by the float32 restatement of the reference alone, on any machine, on the
+    shapes and weight patterns of that test; and by the emulation of the kernel's arithmetic."""
+    from tests import kernel_emulation as emu
+    rng = np.random.default_rng(1000 * S + NI)
+    n = 300
+    t = emu.pdf_rays(n, rng)
+    w = emu.pdf_weights(pattern, n, S, rng)
+    u = rng.uniform(size=(n, NI)).astype(np.float32)
+    for z in (orc.z_values(t, S, np.float32), orc.z_values_perturbed(t, S, seed=5, dtype=np.float32)):
+        mids = np.float32(0.5) * (z[:, 1:] + z[:, :-1])
+        for det in (True, False):
+            z32 = orc.sample_pdf(mids, w[:, 1:-1], NI, det=det, u=None if det else u, dtype=np.float32)
+            emu.pdf_check(np.sort(z32, -1), z, w, t, NI, det, u)
+            emu.pdf_check(np.sort(emu.sample_pdf_f32(z, w, None if det else u, NI), -1), z, w, t, NI, det, u)
+
+
+def test_sin_q_emulation_range():
+    """Where the three-step Cody-Waite reduction of sin_q (nerf_tex_amd/csrc/ntx_device.h) leaves the 2.5e-7 bar of the Fourier
+    features: a float32 emulation of it against float64 sin / cos of the same float32 argument 2^k x, x in [-3, 3].  Inside
+    |2^k x| < 2^17, the domain its comment states and the switch-over point of fourier_kernel, it is within 1.5 ulp of 1; band 19
+    still holds the bar, band 20 does not, and by band 25 the result is not a sine at all.  (python -m tests.kernel_emulation
+    prints the whole table.)"""
+    from tests import kernel_emulation as emu
+    x = np.random.default_rng(1).uniform(-1, 1, 400_000).astype(np.float32) * np.float32(2.0 ** 17)
+    x = x[np.abs(x) < 2.0 ** 17]
+    for q in (0, 1):
+        ref = np.sin(x.astype(np.float64) + q * np.pi / 2) if q == 0 else np.cos(x.astype(np.float64))
+        assert np.max(np.abs(emu.sin_q_f32(x, q) - ref)) <= 1.5 * 2.0 ** -23
+    e = emu.sin_q_band_errors()
+    assert max(e[:20]) <= 2.5e-7
+    assert e[20] > 2.5e-7 and e[22] > 1e-4 and e[25] > 1.0 and e[30] > 1e10
