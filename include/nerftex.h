@@ -485,7 +485,8 @@ int ntx_instancer_set_mesh_textures(ntx_instancer *inst, const float *uv, int64_
  * of network/loss.py:6-59, `tape.gradient`, `optimizer.apply_gradients` with tf.keras.optimizers.Adam under ExponentialDecay
  * (train.py:49-52).  Built for the architecture of the shipped training configs: ParamNerf, depth 8, width 256, skips [4],
  * color_depth 1, Fourier features on n_pos 3 (any n_parameters, any band counts) or -- the MipRenderer's model -- NTX_POS_IPE on n_pos 6
- * (pos_map = 6 pos_freq + n_geo (1 + 2 param_freq) features; ntx_weight_count of the same descriptor); NTX_E_UNSUPPORTED otherwise.  An IPE
+ * (pos_map = 6 pos_freq + n_geo (1 + 2 param_freq) features; ntx_weight_count of the same descriptor); NTX_E_UNSUPPORTED otherwise
+ * (ntx_trainer_create_flex below trains the other architectures, layer by layer).  An IPE
  * trainer has no importance pass: ntx_trainer_composite_weights refuses it (NTX_E_UNSUPPORTED), as the reference's MipRenderer refuses
  * n_importance > 0 (renderer.py:403-404).  The trainer owns the weights
  * (Keras get_weights() order, like ntx_create), Adam's moments, the gradient and every layer's activations for up to
@@ -574,6 +575,21 @@ int ntx_trainer_device_weights(ntx_trainer *t, const float **weights_dev);
  * C[M][N] = op(A) . op(B) (+ bias[N]) (ReLU); a_kcontig: A is [M][K] (row stride lda), else [K][M]; B is [K][N] (b_kcontig must be 0). */
 int ntx_gemm_f32(const float *A, int lda, int a_kcontig, const float *B, int ldb, int b_kcontig, float *C, int ldc, int M, int N, int K, const float *bias,
                  int relu, ntx_stream stream);
+/* A trainer for any architecture the flex render family takes (ABI v7, appended): kind NTX_MODEL_NERF or NTX_MODEL_PARAMNERF, NTX_POS_FOURIER
+ * on n_pos 3, depth 1..24, width 2..256, color_depth 0..4 (0 for a Nerf), skip = one index or NTX_SKIP_MASK | bits with every index below
+ * depth - 1, n_geo <= 4, n_app <= 8, n_freq_bands <= 10 / 4 / 4 -- the 8 x 256 / skips [4] / color_depth 1 shape of ntx_trainer_create
+ * included.  NTX_E_UNSUPPORTED, before any device is asked for: an IPE model, parameter branches (NTX_MODEL_PARAMNERF_EX with
+ * param_depth > 0), a skip at depth - 1, width > 256; then NTX_E_INVALID for max_rays < 1, samples per ray outside 2..1024 or a wrong
+ * n_floats.  The handle is an ordinary ntx_trainer: every ntx_trainer_* entry and ntx_train_step_gradients take it, with the same arguments,
+ * options and meaning; weights, gradients and Adam's moments are in Keras get_weights() order.  The step behind it is one contraction per
+ * Dense layer and pass (the float32 matrix-core kernel of ntx_gemm_f32) on row-major activations kept once each, the narrow heads on small
+ * kernels of their own; weight gradients are partial sums over ranges of 2048 samples added in ascending order, so a step is
+ * bit-reproducible and does not depend on the trainer's capacity.
+ * ntx_trainer_activation on such a handle: layer k = 0 .. n_relu - 1 is the kept output of the k-th ReLU layer in the order trunk 0 ..
+ * depth - 1, colour hidden layers, colour half layer, [n_samples_total][that layer's width]; 64 = the raw density [n_samples_total][1];
+ * 65 = the raw colour [n_samples_total][3]. */
+int ntx_trainer_create_flex(const ntx_model_desc *desc, const float *weights_host, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray,
+                            ntx_trainer **out);
 
 #ifdef __cplusplus
 }

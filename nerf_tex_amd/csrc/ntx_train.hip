@@ -16,6 +16,10 @@
 //                          fixed order (a step is bit-reproducible)
 //   adam_kernel            tf.keras.optimizers.Adam under ExponentialDecay (train.py:49-52), one fused pass over the 2.7 MB of weights
 //
+// Every other architecture the flex render family takes (a plain Nerf; other depths, widths, skips, color_depth) trains behind the same handle
+// layer by layer (ntx_trainer_create_flex): flex_encode_kernel, one gemm_kernel per Dense layer and pass on row-major activations, the narrow
+// heads on flex_head_*_kernel, the same composite_loss_kernel, reduce_batch_kernel and adam_kernel.
+//
 // Everything is float32 with float32 accumulation, like the reference's TensorFlow graph.
 #include "nerftex.h"
 
@@ -626,14 +630,151 @@ __global__ void adam_kernel(float *__restrict__ w, const float *__restrict__ g, 
     w[e] = w[e] - (me * lr_t) / (sqrtf(ve) + eps);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The small kernels of the layer-by-layer step (ntx_trainer_create_flex): any Nerf / ParamNerf the flex render family takes, one
+// gemm_kernel per Dense layer and pass on plain row-major buffers.  A concatenation is a buffer [encoding | hidden] whose two parts
+// are written in place: the encoder writes a map at the front of every buffer that starts with it, the layer in front writes behind it.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int FLEX_MAX_DEPTH = 24, FLEX_MAX_COLOR = 4, FLEX_MAX_DST = FLEX_MAX_DEPTH + 1;
+constexpr int FLEX_SPLIT = 2048;                       // samples per partial sum of a weight gradient: a function of nothing, so a step's sums do not depend on the trainer's capacity
+struct FlexDst { float *p; int ld; };                  // where a map goes: row m starts at p + m * ld
+struct FlexEncodeArgs {
+    const float *rays_o, *rays_d, *z, *params, *cone;
+    long long rays_per_param_row, M;
+    int S, n_geo, n_app, pos_freq, dir_freq, param_freq, blur_idx, Kp, Kd;
+    FlexDst pos[FLEX_MAX_DST], dir; int n_pos_dst;
+    float *dists;
+};
+// encode_kernel's values (the same expressions, ntx::sin_q) as rows [sample][feature]: thread per sample and feature, blockIdx.y = the map
+__global__ __launch_bounds__(256) void flex_encode_kernel(FlexEncodeArgs a) {
+    const int part = blockIdx.y, K = part == 0 ? a.Kp : a.Kd;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.M * K) return;
+    const long long m = e / K, ray = m / a.S;
+    const int f = (int)(e - m * K), s = (int)(m - ray * a.S);
+    const float d[3] = {a.rays_d[3 * ray], a.rays_d[3 * ray + 1], a.rays_d[3 * ray + 2]};
+    const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    const float zr = a.z[(size_t)ray * a.S + s];
+    const bool hit = isfinite(zr);                                                          // a ray that misses the proxy: depth 0, distances 0 (encode_kernel)
+    const float z = hit ? zr : 0.0f;
+    const int P = a.n_geo + a.n_app;
+    const float *pr = P > 0 ? a.params + (size_t)(ray / a.rays_per_param_row) * P : nullptr;
+    auto param = [&](int c) { return c == a.blur_idx ? (hit ? pr[c] * (a.cone[ray] * z) : 0.0f) : pr[c]; };   // renderer.py:155-158
+    const int K3 = 3 * (1 + 2 * (part == 0 ? a.pos_freq : a.dir_freq));
+    const bool xyz = f < K3;
+    const int r = xyz ? f : f - K3, D = xyz ? 3 : (part == 0 ? a.n_geo : a.n_app);
+    auto x = [&](int c) -> float {
+        if (!xyz) return param(part == 0 ? c : a.n_geo + c);                                // model.py:88-93, 96-101
+        const float dc = c == 0 ? d[0] : c == 1 ? d[1] : d[2];
+        return part == 0 ? a.rays_o[3 * ray + c] + dc * z : dc / dn;                        // renderer.py:114, :98
+    };
+    float v;
+    if (r < D) v = x(r);                                                                    // layer.py:14-23: [x | sin(2^0 x) | cos(2^0 x) | ...]
+    else { const int q = r - D, band = q / (2 * D), hc = q - band * 2 * D, h = hc / D, c = hc - h * D; v = ntx::sin_q(ldexpf(1.0f, band) * x(c), h); }
+    if (part == 0) for (int i = 0; i < a.n_pos_dst; ++i) a.pos[i].p[(size_t)m * a.pos[i].ld + f] = v;
+    else {
+        a.dir.p[(size_t)m * a.dir.ld + f] = v;
+        if (f == 0) {                                                                       // renderer.py:174-180
+            const float zn = s + 1 < a.S ? a.z[(size_t)ray * a.S + s + 1] : 0.0f;
+            const float dist = s + 1 < a.S ? zn - z : (a.S > 1 ? z - a.z[(size_t)ray * a.S + s - 1] : 0.0f);
+            a.dists[(size_t)ray * a.S + s] = hit ? dist * dn : 0.0f;
+        }
+    }
+}
+
+// A narrow head (density: 1 column, colour: 3): out[m][c] = b[c] + sum_k X[m][k] W[k][c], K <= 256.  A wave per row, the row's sum
+// in the fixed order of the lanes' butterfly.
+template <int NOUT>
+__global__ __launch_bounds__(256) void flex_head_kernel(const float *__restrict__ X, int ldx, int K, const float *__restrict__ W, const float *__restrict__ b,
+                                                        float *__restrict__ out, long long M) {
+    const int lane = threadIdx.x & 63;
+    const long long n_waves = (long long)gridDim.x * 4;
+    float w[NOUT][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) w[c][q] = lane + 64 * q < K ? W[(lane + 64 * q) * NOUT + c] : 0.0f;
+    for (long long m = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); m < M; m += n_waves) {
+        float acc[NOUT];
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) acc[c] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float x = lane + 64 * q < K ? X[(size_t)m * ldx + lane + 64 * q] : 0.0f;
+#pragma unroll
+            for (int c = 0; c < NOUT; ++c) acc[c] = fmaf(x, w[c][q], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) { acc[c] = wave_sumf(acc[c]); if (lane == 0) out[(size_t)m * NOUT + c] = acc[c] + b[c]; }
+    }
+}
+// ... its weight gradient over one range of FLEX_SPLIT samples: partial[z][k][c] = sum_m X[m][k] dgrad[m][c0 + c], behind it the bias's
+// partial[z][K][c] = sum_m dgrad[m][c0 + c].  1024 threads = G groups of KK >= K threads (KK a power of two >= 64): group g takes the
+// range's samples g, g + G, ... in ascending order, thread k of it column k; the groups' sums are added in ascending g through LDS -- an order
+// that K and the step's sample count fix.  reduce_batch_kernel adds the ranges up.
+template <int NOUT>
+__global__ __launch_bounds__(1024) void flex_head_wgrad_kernel(const float *__restrict__ X, int ldx, int K, int KK, const float *__restrict__ dgrad, int c0, long long M,
+                                                               float *__restrict__ partial) {
+    __shared__ float red[1024 * NOUT], redb[16 * NOUT];
+    const int k = threadIdx.x & (KK - 1), g = threadIdx.x / KK, G = 1024 / KK;
+    const long long m0 = (long long)blockIdx.x * FLEX_SPLIT, m1 = m0 + FLEX_SPLIT < M ? m0 + FLEX_SPLIT : M;
+    float acc[NOUT], bs[NOUT];
+#pragma unroll
+    for (int c = 0; c < NOUT; ++c) acc[c] = bs[c] = 0.0f;
+#pragma unroll 4
+    for (long long m = m0 + g; m < m1; m += G) {
+        const float x = k < K ? X[(size_t)m * ldx + k] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) { const float d = dgrad[4 * m + c0 + c]; acc[c] = fmaf(x, d, acc[c]); bs[c] += d; }
+    }
+#pragma unroll
+    for (int c = 0; c < NOUT; ++c) { red[threadIdx.x * NOUT + c] = acc[c]; if (k == 0) redb[g * NOUT + c] = bs[c]; }
+    __syncthreads();
+    float *p = partial + (size_t)blockIdx.x * ((size_t)K * NOUT + NOUT);
+    if (g == 0 && k < K) {
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) { float sum = 0.0f; for (int q = 0; q < G; ++q) sum += red[(q * KK + k) * NOUT + c]; p[k * NOUT + c] = sum; }
+    }
+    if (threadIdx.x < NOUT) { float sum = 0.0f; for (int q = 0; q < G; ++q) sum += redb[q * NOUT + threadIdx.x]; p[K * NOUT + threadIdx.x] = sum; }
+}
+// ... and the gradient at its input: G[m][k] = sum_c dgrad[m][c0 + c] W[k][c], kept where act[m][k] > 0 (act NULL: everywhere)
+template <int NOUT>
+__global__ __launch_bounds__(256) void flex_head_dx_kernel(const float *__restrict__ dgrad, int c0, const float *__restrict__ W, int K, const float *__restrict__ act,
+                                                           int ldact, float *__restrict__ G, int ldg, long long M) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * K) return;
+    const long long m = e / K; const int k = (int)(e - m * K);
+    float v = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NOUT; ++c) v = fmaf(dgrad[4 * m + c0 + c], W[k * NOUT + c], v);
+    if (act && !(act[(size_t)m * ldact + k] > 0.0f)) v = 0.0f;
+    G[(size_t)m * ldg + k] = v;
+}
+// The hidden rows of every kernel transposed, once a step: wt[dst + j * hid + r] = w[src + r * out + j] -- the [K][N] operand of
+// dX = dY . W^T (the encoding rows of a layer behind a concatenation take no gradient further and are left out)
+struct FlexTSeg { long long src, dst, first, count; int hid, out; };
+__global__ void flex_transpose_kernel(const float *__restrict__ w, float *__restrict__ wt, const FlexTSeg *__restrict__ seg, int n_seg, long long total) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg[mid].first <= e) lo = mid; else hi = mid - 1; }
+    const FlexTSeg &s = seg[lo];
+    const long long o = e - s.first;
+    if (o >= s.count) return;
+    const int j = (int)(o / s.hid), r = (int)(o - (long long)j * s.hid);
+    wt[s.dst + o] = w[s.src + (size_t)r * s.out + j];
+}
+
 }   // namespace ntx_train
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
 struct TLayer { int in, out; size_t w, b; };      // offsets into the Keras-order blob (kernel [in][out], then bias)
+struct FlexState;                                 // a trainer made by ntx_trainer_create_flex: the layer-by-layer step (below)
 
 struct ntx_trainer {
+    FlexState *flex = nullptr;                 // NULL: the chain trainer of ntx_trainer_create
     int device = 0, cus = 256;
     ntx_model_desc desc{};
     int Kp = 0, Kd = 0, P = 0, ptiles = 0, dtiles = 0, PS = 0, DS = 0;   // pos_map / dir_map: features, tiles of 32 rows of their buffers, k-steps of their segments
@@ -669,9 +810,12 @@ namespace {
 using namespace ntx_train;
 
 
+void flex_free(FlexState *f);
+
 void free_all(ntx_trainer *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
+    flex_free(t->flex);
     void *ptrs[] = {t->w, t->grad, t->adam_m, t->adam_v, t->wfwd, t->wdx, t->aux, t->pack_seg, t->posO, t->dirO, t->sigma, t->raw_rgb, t->z, t->dists, t->noise,
                     t->dgrad, t->dhead, t->jobs, t->dw_partial, t->stash, t->dirrow, t->color, t->alpha_out, t->ray_loss, t->loss, t->act, t->bits, t->gout};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -684,6 +828,166 @@ void launch_gemm(hipStream_t st, GemmArgs g) {
     g.k_chunk = g.K;
     g.aligned = (g.lda % 4 == 0) && (g.ldb % 4 == 0) && (((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0);
     hipLaunchKernelGGL((gemm_kernel<AK, 128, 16>), dim3((g.N + 127) / 128, (g.M + TM - 1) / TM, 1), dim3(256), 0, st, g);
+}
+
+// ---- the layer-by-layer trainer (ntx_trainer_create_flex) -----------------------------------------------------------------------
+// A Dense layer with an activation buffer of its own: trunk 0 .. depth-1, the feature layer, the colour layers, the colour half layer
+// (model.py:104-122).  Its input X is the buffer of the layer in front -- [encoding | hidden] where a concatenation lies between them
+// (a skip: pos_map, model.py:107-108; the feature layer: dir_map, :115) --, its output goes to Y = its own buffer behind the encoding
+// columns of the concatenation that follows it.
+struct FlexLayer {
+    int in = 0, out = 0, enc = 0, src = -1, relu = 0;   // enc: the leading input rows that are an encoding (no gradient further); src: the layer whose output the others are
+    size_t w = 0, b = 0;                                // offsets into the Keras-order blob
+    const float *X = nullptr; int ldx = 0;
+    float *Y = nullptr; int ldy = 0;
+    long long wt = -1;                                  // its transposed hidden rows [out][in - enc] in FlexState::wt
+};
+}   // namespace
+
+struct FlexState {
+    std::vector<FlexLayer> layers;
+    std::vector<int> relu_layers;                       // the oracle's mask order: trunk, colour hidden layers, colour half
+    TLayer rgb{}, alpha{};
+    int last_trunk = 0, half = 0;                       // indices into layers
+    int ldg = 0;
+    float *G[2] = {nullptr, nullptr};                   // the gradient at a layer's output, ping-pong
+    float *wt = nullptr; ntx_train::FlexTSeg *tseg = nullptr; int n_tseg = 0; long long t_total = 0;
+    float *partial = nullptr, *colsum = nullptr;        // [n_split][in * out], [n_split][out] of the layer whose weight gradient is being taken
+    ntx_train::FlexDst pos_dst[ntx_train::FLEX_MAX_DST]; int n_pos_dst = 0; ntx_train::FlexDst dir_dst{};
+    std::vector<void *> owned;
+};
+
+namespace {
+
+void flex_free(FlexState *f) {
+    if (!f) return;
+    for (void *p : f->owned) if (p) (void)hipFree(p);
+    delete f;
+}
+
+inline int pad4(int n) { return (n + 3) & ~3; }
+
+unsigned flex_skip_mask(const ntx_model_desc *d) {
+    if (d->skip < 0) return 0u;
+    if (d->skip & NTX_SKIP_MASK) return (unsigned)d->skip & (NTX_SKIP_MASK - 1u);
+    return d->skip < 30 ? 1u << d->skip : 0u;
+}
+
+// the layers of the architecture in forward order with their places in the Keras-order blob (model.layer_table(): trunk, feature, colour
+// hidden layers, colour half, color, alpha); returns the blob's floats
+size_t flex_plan(const ntx_model_desc *d, int Kp, int Kd, FlexState *f) {
+    const int depth = d->depth, w = d->width, cd = d->kind == NTX_MODEL_NERF ? 0 : d->color_depth;
+    const unsigned skips = flex_skip_mask(d) & ((1u << (depth > 1 ? depth - 1 : 0)) - 1u);
+    size_t p = 0;
+    auto add = [&](int in, int out, int enc, int src, int relu) {
+        FlexLayer l; l.in = in; l.out = out; l.enc = enc; l.src = src; l.relu = relu; l.w = p; l.b = p + (size_t)in * out;
+        p += (size_t)in * out + out;
+        f->layers.push_back(l);
+        if (relu) f->relu_layers.push_back((int)f->layers.size() - 1);
+    };
+    for (int i = 0; i < depth; ++i) {
+        const int enc = i == 0 ? Kp : (((skips >> (i - 1)) & 1u) ? Kp : 0);
+        add(i == 0 ? Kp : w + enc, w, enc, i - 1, 1);
+    }
+    f->last_trunk = depth - 1;
+    add(w, w, 0, depth - 1, 0);                                              // the feature layer: no activation (model.py:114)
+    for (int i = 0; i < cd; ++i) add(i == 0 ? w + Kd : w, w, i == 0 ? Kd : 0, depth + i, 1);
+    add(cd > 0 ? w : w + Kd, w / 2, cd > 0 ? 0 : Kd, depth + cd, 1);         // :122
+    f->half = (int)f->layers.size() - 1;
+    f->rgb = TLayer{w / 2, 3, p, p + (size_t)(w / 2) * 3}; p += (size_t)(w / 2) * 3 + 3;
+    f->alpha = TLayer{w, 1, p, p + (size_t)w}; p += (size_t)w + 1;
+    return p;
+}
+
+// gemm_kernel over at most 65 535 row tiles a launch
+template <bool AK>
+void flex_gemm_rows(hipStream_t st, GemmArgs g) {
+    g.k_chunk = g.K;
+    g.aligned = (g.lda % 4 == 0) && (g.ldb % 4 == 0) && (((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0);
+    const long long rows_max = 65535LL * TM, M = g.M;
+    for (long long r0 = 0; r0 < M; r0 += rows_max) {
+        GemmArgs h = g;
+        h.A = g.A + (size_t)r0 * g.lda; h.C = g.C + (size_t)r0 * g.ldc; h.M = (int)std::min<long long>(rows_max, M - r0);
+        if (g.mask) h.mask = g.mask + (size_t)r0 * g.ldmask;
+        hipLaunchKernelGGL((gemm_kernel<AK, 128, 16>), dim3((h.N + 127) / 128, (h.M + TM - 1) / TM, 1), dim3(256), 0, st, h);
+    }
+}
+
+int flex_step(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *params, long long rays_per_param_row, const float *cone_scale, long long n_rays, int S,
+              int blur_idx, const float *z, hipStream_t st) {
+    FlexState *f = t->flex;
+    const long long M = n_rays * S;
+    const float *W = t->w;
+    hipLaunchKernelGGL(flex_transpose_kernel, dim3((unsigned)((f->t_total + 255) / 256)), dim3(256), 0, st, W, f->wt, f->tseg, f->n_tseg, f->t_total);
+    {
+        FlexEncodeArgs e{}; e.rays_o = rays_o; e.rays_d = rays_d; e.z = z; e.params = params; e.cone = cone_scale; e.rays_per_param_row = rays_per_param_row; e.M = M;
+        e.S = S; e.n_geo = t->desc.n_geo; e.n_app = t->desc.n_app; e.pos_freq = t->desc.pos_freq; e.dir_freq = t->desc.dir_freq; e.param_freq = t->desc.param_freq;
+        e.blur_idx = blur_idx; e.Kp = t->Kp; e.Kd = t->Kd; e.n_pos_dst = f->n_pos_dst; e.dir = f->dir_dst; e.dists = t->dists;
+        for (int i = 0; i < f->n_pos_dst; ++i) e.pos[i] = f->pos_dst[i];
+        const long long most = M * std::max(t->Kp, t->Kd);
+        hipLaunchKernelGGL(flex_encode_kernel, dim3((unsigned)((most + 255) / 256), 2), dim3(256), 0, st, e);
+    }
+    // ---- forward: a contraction per layer, every output kept ------------------------------------------------------------------------
+    for (const FlexLayer &l : f->layers) {
+        GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = W + l.w; g.ldb = l.out; g.C = l.Y; g.ldc = l.ldy; g.M = (int)M; g.N = l.out; g.K = l.in; g.bias = W + l.b; g.relu = l.relu;
+        flex_gemm_rows<true>(st, g);
+    }
+    const unsigned head_grid = (unsigned)std::min<long long>((M + 3) / 4, (long long)t->cus * 8);
+    const FlexLayer &lt = f->layers[f->last_trunk], &lh = f->layers[f->half];
+    hipLaunchKernelGGL(flex_head_kernel<1>, dim3(head_grid), dim3(256), 0, st, lt.Y, lt.ldy, lt.out, W + f->alpha.w, W + f->alpha.b, t->sigma, M);      // model.py:111
+    hipLaunchKernelGGL(flex_head_kernel<3>, dim3(head_grid), dim3(256), 0, st, lh.Y, lh.ldy, lh.out, W + f->rgb.w, W + f->rgb.b, t->raw_rgb, M);        // :123
+    return NTX_OK;
+}
+
+// the way back from the composite's adjoint dgrad [M][4]: per layer, last to first, dW = X^T . dY over ranges of FLEX_SPLIT samples added in
+// ascending order, then dX = (dY . W[hidden rows]^T) where the stored activation in front is > 0
+void flex_backward(ntx_trainer *t, long long M, hipStream_t st) {
+    FlexState *f = t->flex;
+    const float *W = t->w;
+    const int n_split = (int)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
+    auto reduce = [&](const float *partial, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
+        ReduceBatch rb{};
+        rb.job[0] = ReduceJob{partial, n_split, count, count, 0, t->grad + out, 0};
+        rb.n = 1;
+        long long total = (count + 255) / 256 * 256;
+        if (bias_partial) { rb.job[1] = ReduceJob{bias_partial, n_split, bias_count, bias_count, 0, t->grad + bias_out, total}; rb.n = 2; total += (bias_count + 255) / 256 * 256; }
+        hipLaunchKernelGGL(reduce_batch_kernel, dim3((unsigned)(total / 256)), dim3(256), 0, st, rb);
+    };
+    const FlexLayer &lt = f->layers[f->last_trunk], &lh = f->layers[f->half];
+    const unsigned ew = 256;
+    // the colour head (model.py:123): kernel and bias lie side by side in the blob, as in a range's partial sums
+    auto pow2 = [](int k) { int p = 64; while (p < k) p *= 2; return p; };
+    hipLaunchKernelGGL(flex_head_wgrad_kernel<3>, dim3((unsigned)n_split), dim3(1024), 0, st, lh.Y, lh.ldy, lh.out, pow2(lh.out), t->dgrad, 0, M, f->partial);
+    reduce(f->partial, (long long)lh.out * 3 + 3, f->rgb.w, nullptr, 0, 0);
+    int cur = 0;
+    hipLaunchKernelGGL(flex_head_dx_kernel<3>, dim3((unsigned)((M * lh.out + ew - 1) / ew)), dim3(ew), 0, st, t->dgrad, 0, W + f->rgb.w, lh.out, lh.Y, lh.ldy, f->G[cur], f->ldg, M);
+    for (int i = (int)f->layers.size() - 1; i >= 0; --i) {
+        const FlexLayer &l = f->layers[i];
+        const float *dY = f->G[cur];
+        {   // dW_i and db_i
+            GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = f->ldg; g.C = f->partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
+            g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = f->colsum;
+            g.aligned = (g.lda % 4 == 0) && (g.ldb % 4 == 0) && (((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0);
+            hipLaunchKernelGGL((gemm_kernel<false, 128, 16>), dim3((g.N + 127) / 128, (g.M + TM - 1) / TM, (unsigned)n_split), dim3(256), 0, st, g);
+            reduce(f->partial, (long long)l.in * l.out, l.w, f->colsum, l.out, l.b);
+        }
+        if (i == 0) break;                                                   // the inputs are not trained
+        const FlexLayer &s = f->layers[l.src];
+        float *dX = f->G[cur ^ 1];
+        int accumulate = 0;
+        if (l.src == f->last_trunk) {                                        // the density head hangs on the same output (model.py:111): its rank-1 term first
+            hipLaunchKernelGGL(flex_head_wgrad_kernel<1>, dim3((unsigned)n_split), dim3(1024), 0, st, lt.Y, lt.ldy, lt.out, pow2(lt.out), t->dgrad, 3, M, f->partial);
+            reduce(f->partial, (long long)lt.out + 1, f->alpha.w, nullptr, 0, 0);
+            hipLaunchKernelGGL(flex_head_dx_kernel<1>, dim3((unsigned)((M * lt.out + ew - 1) / ew)), dim3(ew), 0, st, t->dgrad, 3, W + f->alpha.w, lt.out, (const float *)nullptr, 0, dX,
+                               f->ldg, M);
+            accumulate = 1;
+        }
+        GemmArgs g{}; g.A = dY; g.lda = f->ldg; g.B = f->wt + l.wt; g.ldb = l.in - l.enc; g.C = dX; g.ldc = f->ldg; g.M = (int)M; g.N = l.in - l.enc; g.K = l.out;
+        g.accumulate = accumulate;
+        if (s.relu) { g.mask = s.Y; g.ldmask = s.ldy; }
+        flex_gemm_rows<true>(st, g);
+        cur ^= 1;
+    }
 }
 
 }   // namespace
@@ -718,7 +1022,7 @@ int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t 
     if (desc->kind != NTX_MODEL_PARAMNERF || desc->depth != 8 || desc->width != 256 || desc->skip != 4 || desc->color_depth != 1 ||
         !((desc->pos_encoding == NTX_POS_FOURIER && desc->n_pos == 3) || ipe))
         return ntx_set_error(NTX_E_UNSUPPORTED, "training is built for the ParamNerf architecture of the shipped training configs (depth 8, width 256, skips [4], color_depth 1, "
-                                                "Fourier features on n_pos 3 or IPE on n_pos 6); others render but do not train");
+                                                "Fourier features on n_pos 3 or IPE on n_pos 6); other architectures train through ntx_trainer_create_flex");
     if (desc->n_geo < 0 || desc->n_app < 0 || desc->n_geo + desc->n_app > 16) return ntx_set_error(NTX_E_INVALID, "n_parameters out of range");
     if (desc->pos_freq < 0 || desc->dir_freq < 0 || desc->param_freq < 0) return ntx_set_error(NTX_E_INVALID, "negative band count");
     const int Kp = (ipe ? 6 * desc->pos_freq : 3 * (1 + 2 * desc->pos_freq)) + desc->n_geo * (1 + 2 * desc->param_freq), Kd = 3 * (1 + 2 * desc->dir_freq) + desc->n_app * (1 + 2 * desc->param_freq);
@@ -911,6 +1215,103 @@ int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t 
     return NTX_OK;
 }
 
+int ntx_trainer_create_flex(const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
+    if (!out) return ntx_set_error(NTX_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!desc || !weights) return ntx_set_error(NTX_E_INVALID, "desc / weights is NULL");
+    // the architectures the flex render family takes (nerftex.hip: find_variant) without parameter branches
+    const bool nerf = desc->kind == NTX_MODEL_NERF;
+    if (desc->kind != NTX_MODEL_PARAMNERF && desc->kind != NTX_MODEL_NERF && desc->kind != NTX_MODEL_PARAMNERF_EX) return ntx_set_error(NTX_E_UNSUPPORTED, "training: model kind %d", desc->kind);
+    if (desc->kind == NTX_MODEL_PARAMNERF_EX && desc->n_geo + desc->n_app > 0 && reinterpret_cast<const ntx_model_desc_ex *>(desc)->param_depth != 0)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: parameter branches (param_depth > 0) render but do not train");
+    if (desc->pos_encoding != NTX_POS_FOURIER || desc->n_pos != 3)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "the layer-by-layer trainer takes Fourier features on n_pos 3 (an IPE model trains in the 8 x 256 / skips [4] / color_depth 1 shape: ntx_trainer_create)");
+    const int n_geo = nerf ? 0 : desc->n_geo, n_app = nerf ? 0 : desc->n_app, cd = nerf ? 0 : desc->color_depth;
+    if (desc->depth < 1 || desc->depth > FLEX_MAX_DEPTH || desc->width < 2 || desc->width > 256 || cd < 0 || cd > FLEX_MAX_COLOR)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: depth %d width %d color_depth %d (built: depth 1..%d, width 2..256, color_depth 0..%d)", desc->depth, desc->width, cd,
+                             FLEX_MAX_DEPTH, FLEX_MAX_COLOR);
+    if ((desc->skip >= 0 && !(desc->skip & NTX_SKIP_MASK) && desc->skip >= 30) || ((flex_skip_mask(desc) >> (desc->depth - 1)) & 1u))
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: a skip behind the last trunk layer (it widens the density head and the feature layer, model.py:107-114) is not built");
+    if (n_geo < 0 || n_geo > 4 || n_app < 0 || n_app > 8 || desc->pos_freq < 0 || desc->pos_freq > 10 || desc->dir_freq < 0 || desc->dir_freq > 4 ||
+        (n_geo + n_app > 0 && (desc->param_freq < 0 || desc->param_freq > 4)))
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: n_parameters [%d,%d] / band counts %d %d %d (built: [g<=4, a<=8], bands <= 10 / 4 / 4)", n_geo, n_app, desc->pos_freq,
+                             desc->dir_freq, desc->param_freq);
+    if (max_rays < 1 || max_samples_per_ray < 2 || max_samples_per_ray > MAX_TRAIN_SAMPLES || max_rays * (int64_t)max_samples_per_ray > (int64_t)1 << 30)
+        return ntx_set_error(NTX_E_INVALID, "max_rays / max_samples_per_ray out of range (samples per ray <= %d)", MAX_TRAIN_SAMPLES);
+    const int pfq = n_geo + n_app > 0 ? desc->param_freq : 0;
+    const int Kp = 3 * (1 + 2 * desc->pos_freq) + n_geo * (1 + 2 * pfq), Kd = 3 * (1 + 2 * desc->dir_freq) + n_app * (1 + 2 * pfq);
+    FlexState *f = new FlexState();
+    const size_t p = flex_plan(desc, Kp, Kd, f);
+    if (n_floats != p) { delete f; return ntx_set_error(NTX_E_INVALID, "weights: %zu floats, the model has %zu", n_floats, p); }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { delete f; return ntx_set_error(NTX_E_NODEVICE, "no HIP device visible"); }
+    if (device < 0 || device >= ndev) { delete f; return ntx_set_error(NTX_E_INVALID, "device %d out of range [0,%d)", device, ndev); }
+    ntx_trainer *t = new ntx_trainer();
+    t->flex = f; t->device = device; t->desc = *desc; t->desc.n_geo = n_geo; t->desc.n_app = n_app; t->desc.param_freq = pfq;
+    t->P = n_geo + n_app; t->Kp = Kp; t->Kd = Kd; t->n_weights = p;
+    const long long M = (long long)max_rays * max_samples_per_ray, NB = (M + 31) / 32;
+    t->cap = M; t->cap_rays = max_rays; t->cap_blocks = NB;
+    int rc = hipSetDevice(device) == hipSuccess ? NTX_OK : ntx_set_error(NTX_E_HIP, "hipSetDevice(%d) failed", device);
+    if (rc == NTX_OK) { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) t->cus = n; }
+    auto alloc = [&](float **d, size_t n, bool zero = false) -> int {
+        if (rc != NTX_OK) return rc;
+        if (hipMalloc((void **)d, (n ? n : 1) * sizeof(float)) != hipSuccess) return rc = ntx_set_error(NTX_E_HIP, "hipMalloc of %zu floats failed", n);
+        if (zero && hipMemset(*d, 0, (n ? n : 1) * sizeof(float)) != hipSuccess) return rc = ntx_set_error(NTX_E_HIP, "hipMemset failed");
+        return rc;
+    };
+    auto own = [&](float **d, size_t n, bool zero = false) { alloc(d, n, zero); if (*d) f->owned.push_back(*d); };     // freed with the FlexState; the others by free_all
+    alloc(&t->w, p); alloc(&t->grad, p, true); alloc(&t->adam_m, p, true); alloc(&t->adam_v, p, true);
+    alloc(&t->sigma, (size_t)M); alloc(&t->raw_rgb, (size_t)M * 3); alloc(&t->z, (size_t)M); alloc(&t->dists, (size_t)M); alloc(&t->noise, (size_t)M);
+    alloc(&t->dgrad, (size_t)NB * 32 * 4); alloc(&t->dhead, (size_t)NB * 1024);                 // (dhead: the chain's copy of the adjoint, which composite_loss_kernel also writes)
+    alloc(&t->color, (size_t)max_rays * 3); alloc(&t->alpha_out, (size_t)max_rays); alloc(&t->ray_loss, (size_t)max_rays); alloc(&t->loss, 1);
+    if (rc == NTX_OK && hipMemcpy(t->w, weights, p * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = ntx_set_error(NTX_E_HIP, "weight upload failed");
+    // ---- a buffer per layer, [the encoding of the concatenation behind it | its output], rows padded to 16 bytes; the first layer reads pos_map
+    const unsigned skips = flex_skip_mask(desc) & ((1u << (desc->depth > 1 ? desc->depth - 1 : 0)) - 1u);
+    float *pos = nullptr;
+    own(&pos, (size_t)M * pad4(Kp));
+    f->pos_dst[f->n_pos_dst++] = FlexDst{pos, pad4(Kp)};
+    std::vector<float *> base(f->layers.size(), nullptr);
+    std::vector<int> front(f->layers.size(), 0);
+    size_t most_dw = 1024;                                                 // (the heads' partial sums: at most 128 x 3 + 3 floats a range)
+    for (size_t i = 0; i < f->layers.size(); ++i) {
+        FlexLayer &l = f->layers[i];
+        front[i] = (int)i < desc->depth ? (((skips >> i) & 1u) ? Kp : 0) : ((int)i == desc->depth ? Kd : 0);
+        l.ldy = pad4(front[i] + l.out);
+        own(&base[i], (size_t)M * l.ldy);
+        l.Y = base[i] ? base[i] + front[i] : nullptr;
+        if ((int)i < desc->depth && front[i]) f->pos_dst[f->n_pos_dst++] = FlexDst{base[i], l.ldy};
+        if ((int)i == desc->depth) f->dir_dst = FlexDst{base[i], l.ldy};
+        if (i == 0) { l.X = pos; l.ldx = pad4(Kp); }
+        else { l.X = base[l.src]; l.ldx = f->layers[l.src].ldy; }                           // (the whole row: encoding columns first, as the kernel's rows are)
+        most_dw = std::max(most_dw, (size_t)l.in * l.out);
+    }
+    f->ldg = pad4(desc->width);
+    own(&f->G[0], (size_t)M * f->ldg); own(&f->G[1], (size_t)M * f->ldg);
+    const size_t splits = (size_t)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
+    own(&f->partial, splits * most_dw); own(&f->colsum, splits * 256);
+    std::vector<FlexTSeg> segs;
+    long long at = 0;
+    for (size_t i = 1; i < f->layers.size(); ++i) {
+        FlexLayer &l = f->layers[i];
+        const int hid = l.in - l.enc;
+        l.wt = at;
+        segs.push_back(FlexTSeg{(long long)(l.w + (size_t)l.enc * l.out), at, at, (long long)hid * l.out, hid, l.out});
+        at += ((long long)hid * l.out + 3) / 4 * 4;
+    }
+    f->t_total = at; f->n_tseg = (int)segs.size();
+    own(&f->wt, (size_t)at);
+    if (rc == NTX_OK) {
+        if (hipMalloc((void **)&f->tseg, segs.size() * sizeof(FlexTSeg)) != hipSuccess) rc = ntx_set_error(NTX_E_HIP, "segment table allocation failed");
+        else {
+            f->owned.push_back(f->tseg);
+            if (hipMemcpy(f->tseg, segs.data(), segs.size() * sizeof(FlexTSeg), hipMemcpyHostToDevice) != hipSuccess) rc = ntx_set_error(NTX_E_HIP, "segment table upload failed");
+        }
+    }
+    if (rc != NTX_OK) { free_all(t); return rc; }
+    *out = t;
+    return NTX_OK;
+}
+
 int ntx_trainer_destroy(ntx_trainer *t) { free_all(t); return NTX_OK; }
 
 size_t ntx_trainer_weight_count(const ntx_trainer *t) { return t ? t->n_weights : 0; }
@@ -933,6 +1334,19 @@ int ntx_trainer_get(ntx_trainer *t, int what, float *out_host, size_t n_floats) 
 int ntx_trainer_activation(ntx_trainer *t, int layer, int64_t n_samples_total, float *out_host) {
     if (!t || !out_host) return ntx_set_error(NTX_E_INVALID, "NULL argument");
     if (n_samples_total < 1 || n_samples_total > t->cap) return ntx_set_error(NTX_E_INVALID, "n_samples_total out of range");
+    if (t->flex) {                                                                              // row-major buffers: a strided copy
+        const FlexState *f = t->flex;
+        const float *from = nullptr; int width = 0, ld = 0;
+        if (layer >= 0 && layer < (int)f->relu_layers.size()) { const FlexLayer &l = f->layers[f->relu_layers[layer]]; from = l.Y; width = l.out; ld = l.ldy; }
+        else if (layer == 64) { from = t->sigma; width = ld = 1; }
+        else if (layer == 65) { from = t->raw_rgb; width = ld = 3; }
+        else return ntx_set_error(NTX_E_INVALID, "layer %d (0 .. %d: the ReLU layers in the order trunk, colour layers, colour half; 64 the raw density, 65 the raw colour)", layer,
+                                  (int)f->relu_layers.size() - 1);
+        TRAIN_TRY(hipSetDevice(t->device));
+        TRAIN_TRY(hipDeviceSynchronize());
+        TRAIN_TRY(hipMemcpy2D(out_host, (size_t)width * sizeof(float), from, (size_t)ld * sizeof(float), (size_t)width * sizeof(float), (size_t)n_samples_total, hipMemcpyDeviceToHost));
+        return NTX_OK;
+    }
     const float *src = nullptr; int tiles = 8;
     auto act = [&](int i) { return t->act + (size_t)i * t->act_stride; };
     auto gout = [&](int i) { return t->gout + (size_t)i * t->gout_stride; };
@@ -1043,7 +1457,7 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
     hipStream_t st = (hipStream_t)stream;
     const long long M = (long long)n_rays * n_samples;
     const int S = n_samples, n_blocks = (int)((M + 31) / 32);
-    {
+    if (!t->flex) {
         PackArgs pa{t->pack_seg, t->n_pack, t->pack_total};
         hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((t->pack_total + 255) / 256)), dim3(256), 0, st, pa);
     }
@@ -1060,7 +1474,10 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         if (rc != NTX_OK) return rc;
         noise = t->noise;
     }
-    {
+    if (t->flex) {                                                                              // a contraction per layer instead of the chain
+        int rc = flex_step(t, rays_o, rays_d, params, rays_per_param_row, cone_scale, n_rays, S, blur_idx, z, st);
+        if (rc != NTX_OK) return rc;
+    } else {
         EncodeArgs e{}; e.rays_o = rays_o; e.rays_d = rays_d; e.z = z; e.params = params; e.cone = cone_scale; e.rays_per_param_row = rays_per_param_row; e.M = M;
         e.n_rays = (int)n_rays; e.S = S; e.n_geo = t->desc.n_geo; e.n_app = t->desc.n_app; e.pos_freq = t->desc.pos_freq; e.dir_freq = t->desc.dir_freq;
         e.param_freq = t->desc.param_freq; e.blur_idx = blur_idx; e.posO = t->posO; e.ptiles = t->ptiles; e.dirO = t->dirO;
@@ -1069,7 +1486,7 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         else hipLaunchKernelGGL(encode_kernel, dim3((unsigned)n_blocks, 2), dim3(64), 0, st, e);
     }
     const unsigned chain_grid = (unsigned)std::min<long long>(t->cus, (n_blocks + 3) / 4);      // persistent: a workgroup of four waves per CU
-    {
+    if (!t->flex) {
         FwdArgs f{}; f.stream = t->wfwd; f.stream_bytes = (uint32_t)(t->fwd_floats * sizeof(float)); f.aux = t->aux; f.M = M;
         f.ptiles = t->ptiles; f.dtiles = t->dtiles; f.pos = t->posO; f.dir = t->dirO;
         f.act = t->act; f.act_stride = t->act_stride; f.bits = t->bits; f.bits_stride = t->bits_stride;
@@ -1101,6 +1518,11 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, t->ray_loss, (int)n_rays, loss_out ? loss_out : t->loss);
     }
     // ---- backward -----------------------------------------------------------------------------------------------------------------
+    if (t->flex) {
+        flex_backward(t, M, st);
+        TRAIN_TRY(hipGetLastError());
+        return NTX_OK;
+    }
     {
         DxArgs d{}; d.stream = t->wdx; d.stream_bytes = (uint32_t)(t->dx_floats * sizeof(float)); d.M = M; d.dgrad = t->dgrad;
         d.out = t->gout; d.out_stride = t->gout_stride; d.bits = t->bits; d.bits_stride = t->bits_stride;

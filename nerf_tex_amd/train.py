@@ -10,8 +10,12 @@ dicts), model, loss, schedule and renderer from the config blocks, the loop, and
 views rendered through the inference path with the trainer's weights handed over on the device, checkpoints in TensorFlow's bundle format
 with model + step + optimizer (train.py:55-57) that `Trainer.restore` resumes from.
 
-Built for the ParamNerf architecture of the shipped training configs (8 x 256, skips [4], color_depth 1; narrower widths inside it), with
-FourierFeatures under the Renderer or -- an IntegratedPositionalEncoding model (n_pos 6) -- under the MipRenderer (renderer.py:356-473)."""
+`Trainer` is built for the ParamNerf architecture of the shipped training configs (8 x 256, skips [4], color_depth 1; narrower widths inside
+it), with FourierFeatures under the Renderer or -- an IntegratedPositionalEncoding model (n_pos 6) -- under the MipRenderer
+(renderer.py:356-473): three fused passes over the layer chain.  `FlexTrainer` trains every other Nerf / ParamNerf the renderer's flex family
+takes (FourierFeatures; depth 1..24, width 2..256, color_depth 0..4, skips below depth-1, no parameter branches) layer by layer: one
+contraction per Dense layer and pass (`ntx_trainer_create_flex`).  `trainer_for(model, ...)` picks between them, and `Trainer.from_config`,
+`CoarseFineTrainer` and `Train` build their trainers through it."""
 
 from __future__ import annotations
 
@@ -46,19 +50,21 @@ class Trainer:
         blob = np.ascontiguousarray(model.get_blob(), dtype=np.float32)
         self._h = C.c_void_p()
         self._pad = None
-        wide = _widened(model)
+        wide = self._widen(model)
         if wide is not None:                                                    # a narrower network trains inside the 256-wide one (see _widened)
             self._pad = _narrow_in_wide(model, wide)
             full = np.zeros(wide.n_weight_floats(), np.float32)
             full[self._pad] = blob
             blob = full
         desc = (wide or model).desc()
-        _lib.check(_lib.lib.ntx_trainer_create(C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, self.device, self.max_rays,
-                                               self.n_samples, C.byref(self._h)))
+        _lib.check(self._create(C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, self.device, self.max_rays, self.n_samples, C.byref(self._h)))
         self._n_native = int(_lib.lib.ntx_trainer_weight_count(self._h))
         self.n_weights = self._n_native if self._pad is None else int(self._pad.size)
         self._calls = 0
         self._last_rays = 0
+
+    _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create(*a))           # the entry that makes the native trainer
+    _widen = staticmethod(lambda model: _widened(model))                           # a narrower network inside the 256-wide one
 
     @classmethod
     def from_config(cls, config: dict, max_rays: Optional[int] = None, device: int = 0, weights=None):
@@ -93,7 +99,7 @@ class Trainer:
             raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "IPE models train under MipRenderer, FourierFeatures models under Renderer")
         if n_importance > 0:                                                    # renderer.py:125-138: a coarse and a fine pass
             return CoarseFineTrainer(model, models.get(model.name + "_fine"), n_importance=n_importance, **kw), loss
-        return cls(model, **kw), loss
+        return (trainer_for if cls is Trainer else cls)(model, **kw), loss      # the chain where it takes the model, layer by layer otherwise
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -284,6 +290,67 @@ class Trainer:
         return val
 
 
+class FlexTrainer(Trainer):
+    """`Trainer` for the architectures the fused chain does not take: any Nerf / ParamNerf of the renderer's flex family (FourierFeatures on
+    n_pos 3, depth 1..24, width 2..256, color_depth 0..4, skips below depth-1, param_depth 0 -- the chain's own 8 x 256 shape included), one
+    contraction per Dense layer and pass behind `ntx_trainer_create_flex`.  Same constructor, same steps, state, checkpoints and all-reduce;
+    weights and gradients in `get_weights()` order."""
+
+    _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create_flex(*a))
+    _widen = staticmethod(lambda model: None)                                      # every width trains as it is
+
+    def relu_widths(self):
+        """Widths of the ReLU layers in the order of `activation`'s indices (and of the oracle's masks): trunk, colour layers, colour half."""
+        m = self.model
+        cd = m.color_depth if m.kind == 0 else 0
+        return [m.width] * (m.depth + cd) + [m.width // 2]
+
+    def activation(self, layer: int, n_samples_total: int):
+        """What the last step kept: `layer` 0 .. n_relu - 1 the output of the k-th ReLU layer (trunk 0 .. depth-1, colour hidden layers, colour
+        half layer), 64 the raw density, 65 the raw colour: [n_samples_total, width] float32 (tests)."""
+        import numpy as np
+        widths = self.relu_widths()
+        width = {64: 1, 65: 3}.get(int(layer)) or (widths[int(layer)] if 0 <= int(layer) < len(widths) else 1)
+        out = np.empty((int(n_samples_total), width), np.float32)
+        _lib.check(_lib.lib.ntx_trainer_activation(self._h, int(layer), int(n_samples_total), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+
+def _chain_takes(model) -> bool:
+    """Whether `Trainer` (the fused chain, `ntx_trainer_create`) trains `model`: ParamNerf 8 x 256 / skips [4] / color_depth 1 with Fourier
+    features or IPE and encodings of at most 96 features, or a narrower Fourier network that `_widened` pads into it."""
+    from .model import KIND_PARAMNERF
+    live = sorted({int(i) for i in model.skips if 0 <= int(i) < model.depth})
+    if not (model.kind == KIND_PARAMNERF and model.depth == 8 and live == [4] and model.color_depth == 1 and model.param_depth == 0):
+        return False
+    if max(model.pos_map_dim, model.dir_map_dim) > 96:
+        return False
+    ipe = model.pos_encoding == "ipe"
+    if model.width == 256:
+        return model.n_pos == (6 if ipe else 3)
+    return _widened(model) is not None and model.n_pos == 3
+
+
+def trainer_class_for(model):
+    """The class that trains `model`, without creating anything (no device is asked for): `Trainer` where the fused chain takes it,
+    `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise."""
+    import numpy as np
+    if _chain_takes(model):
+        return Trainer
+    desc, h = model.desc(), C.c_void_p()
+    blob = np.zeros(max(1, model.n_weight_floats()), np.float32)
+    # the entry checks the architecture first (NTX_E_UNSUPPORTED) and max_rays = 0 next (NTX_E_INVALID), before anything is created
+    rc = _lib.lib.ntx_trainer_create_flex(C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, 0, 0, 0, C.byref(h))
+    if rc != _lib.NTX_E_INVALID:                                                   # NTX_E_UNSUPPORTED, with the library's own words
+        _lib.check(rc)
+    return FlexTrainer
+
+
+def trainer_for(model, **kw):
+    """`Trainer(model, **kw)` or `FlexTrainer(model, **kw)`, whichever `trainer_class_for` names."""
+    return trainer_class_for(model)(model, **kw)
+
+
 class CoarseFineTrainer:
     """Training with `n_importance > 0` (renderer.py:125-138, loss.py:15-16, 41-47, model.py:47-56): a coarse pass on `n_samples` depths, the
     importance sampler on its composite weights (sample_pdf, no gradient through it: `tf.stop_gradient`, :129), a fine pass on the
@@ -297,8 +364,8 @@ class CoarseFineTrainer:
         if self.n_importance < 1:
             raise ValueError("n_importance must be >= 1 (a plain Trainer otherwise)")
         total = self.n_samples + self.n_importance
-        self.fine = Trainer(model if self.shared else model_fine, max_rays=max_rays, n_samples=total, **kw)
-        self.coarse = self.fine if self.shared else Trainer(model, max_rays=max_rays, n_samples=self.n_samples, **kw)
+        self.fine = trainer_for(model if self.shared else model_fine, max_rays=max_rays, n_samples=total, **kw)
+        self.coarse = self.fine if self.shared else trainer_for(model, max_rays=max_rays, n_samples=self.n_samples, **kw)
         self.model, self.model_fine, self.device, self.perturb = model, model_fine, self.fine.device, self.fine.perturb
         self._calls = 0
 

@@ -1,0 +1,99 @@
+"""The layer-by-layer training step (`FlexTrainer`, ntx_trainer_create_flex) beside the fused chain (`Trainer`), 1024 rays x 256 samples, perturb,
+AlphaLoss(smape, mse) + Adam, timed with HIP events over whole steps:
+    A  the carpet model (ParamNerf [1, 6], 8 x 256, skips [4], color_depth 1) through Trainer
+    B  the same model through FlexTrainer      (B / A on one model is the ratio that matters)
+    C  a plain Nerf 8 x 256 through FlexTrainer
+    D  a ParamNerf [1, 6] of width 128, depth 4 through FlexTrainer
+A and B alternate twice in one process so that clock drift shows.
+    python tools/bench_train_flex.py [--steps 20] [--warmup 5] [--only B] [--out profiles/train_flex/bench.json]
+One JSON line: per run ms a step, ray-samples/s and the fraction of the f32 matrix cores' peak the FLOPs a step needs take (bench.py's
+convention for training: 2 x forward + forward less the encoded inputs' rows)."""
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+PEAK_F32_MFMA = 157.3e12          # MI355X: 256 CUs x 256 f32 matrix FLOPs a clock x 2.4 GHz
+
+
+def step_flops(model, samples):
+    """Forward and weight gradients of every layer, input gradients of all rows but the encoded inputs' (layer 0, pos_map behind a skip, dir_map
+    behind the feature layer)."""
+    table = model.layer_table()
+    macs = model.macs_per_sample()
+    names = [name for name, _, _ in table]
+    behind_feature = names[names.index("feature") + 1]
+    enc = sum((i if name == "trunk0" else i - model.width) * o for name, i, o in table if name.startswith("trunk") or name == behind_feature)
+    return 2.0 * samples * (3 * macs - enc)
+
+
+def time_steps(tr, args, loss, steps, warmup, **kw):
+    for _ in range(warmup):
+        tr.step(*args, loss, **kw)
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(steps):
+        tr.step(*args, loss, **kw)
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / 1e3 / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--only", default=None, help="one of A B C D (a profiler's run)")
+    ap.add_argument("--out", default=None, help="also write the JSON here")
+    a = ap.parse_args()
+    from nerf_tex_amd import synthetic
+    from nerf_tex_amd.loss import AlphaLoss
+    from nerf_tex_amd.model import Nerf, ParamNerf
+    from nerf_tex_amd.train import FlexTrainer, Trainer
+    B, R, S = 4, 256, 256
+    n = B * R
+    f = synthetic.FAMILIES["carpet"]
+    ro, rd, t, cone = synthetic.all_hit_rays(n, f["b_0"], f["b_1"], f["cam"])
+    rng = np.random.default_rng(0)
+    color = rng.uniform(0, 1, (n, 3)).astype(np.float32); alpha = rng.uniform(0, 1, n).astype(np.float32)
+    params = np.asarray([f["params"]] * B, np.float32) * rng.uniform(0.8, 1.2, (B, 7)).astype(np.float32)
+    dev = torch.device("cuda", 0)
+    d = lambda x: torch.as_tensor(x, device=dev)
+    loss = AlphaLoss(loss_fn="network.loss.smape", alpha_loss_fn="network.loss.mse")
+    emb = lambda k: {"module": "network.model.FourierFeatures", "n_freq_bands": k}
+    seeded = lambda m: (m.set_blob(synthetic.synthetic_weights(m.layer_table(), seed=0, dense_media=True)), m)[1]
+    carpet = seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6])["model"])
+    runs = {"A": (Trainer, carpet), "B": (FlexTrainer, carpet), "C": (FlexTrainer, seeded(Nerf(emb(10), emb(4))["model"])),
+            "D": (FlexTrainer, seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6], width=128, depth=4)["model"]))}
+    order = [a.only] if a.only else ["A", "B", "A", "B", "C", "D"]
+    out = {"what": "training step, 1024 rays x 256 samples, perturb, AlphaLoss(smape, mse) + Adam; HIP events", "steps": a.steps, "warmup": a.warmup, "runs": []}
+    trainers = {}
+    for key in order:
+        cls, model = runs[key]
+        if key not in trainers:
+            trainers[key] = cls(model, max_rays=n, n_samples=S, lrate=5e-4, lrate_decay=500, perturb=True)
+        batch = (d(ro), d(rd), d(t), d(params) if model.n_params else None, d(cone), d(color), d(alpha))
+        sec = time_steps(trainers[key], batch, loss, a.steps, a.warmup, rays_per_param_row=R)
+        fl = step_flops(model, n * S)
+        out["runs"].append({"run": key, "trainer": cls.__name__, "model": f"{'Nerf' if model.kind else 'ParamNerf'} {model.depth} x {model.width}", "ms_step": 1e3 * sec,
+                            "ray_samples_per_s": n * S / sec, "gflop_step": fl / 1e9, "fraction_of_f32_mfma_peak": fl / sec / PEAK_F32_MFMA})
+    ms = lambda k: [r["ms_step"] for r in out["runs"] if r["run"] == k]
+    if ms("A") and ms("B"):
+        out["B_over_A"] = float(np.mean(ms("B")) / np.mean(ms("A")))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
