@@ -1,0 +1,355 @@
+// ntx_backend_flex.hip -- the layer-by-layer backend of a training step (ntx_trainer_create_flex): any Nerf / ParamNerf the flex render
+// family takes (other depths, widths, skips, color_depth) on row-major activations -- flex_encode_kernel, one contraction (ntx_gemm.hip) per
+// Dense layer and pass, the narrow heads on flex_head_*_kernel.  The handle, the composite, the loss and Adam are ntx_trainer.hip's.  gfx950 only.
+#include <algorithm>
+#include "ntx_trainer.h"
+#include "ntx_encode.h"
+namespace ntx_train {
+// ---------------------------------------------------------------------------------------------------------------------------
+// The small kernels of the layer-by-layer step (ntx_trainer_create_flex): any Nerf / ParamNerf the flex render family takes, one
+// gemm_kernel per Dense layer and pass on plain row-major buffers.  A concatenation is a buffer [encoding | hidden] whose two parts
+// are written in place: the encoder writes a map at the front of every buffer that starts with it, the layer in front writes behind it.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int FLEX_MAX_DEPTH = 24, FLEX_MAX_COLOR = 4, FLEX_MAX_DST = FLEX_MAX_DEPTH + 1;
+constexpr int FLEX_SPLIT = 2048;                       // samples per partial sum of a weight gradient: a function of nothing, so a step's sums do not depend on the trainer's capacity
+struct FlexDst { float *p; int ld; };                  // where a map goes: row m starts at p + m * ld
+struct FlexEncodeArgs {
+    StepRays r; int Kp, Kd;
+    FlexDst pos[FLEX_MAX_DST], dir; int n_pos_dst;
+    float *dists;
+};
+// ntx_encode.h's values as rows [sample][feature]: thread per sample and feature, blockIdx.y = the map
+__global__ __launch_bounds__(256) void flex_encode_kernel(FlexEncodeArgs args) {
+    const StepRays &a = args.r;
+    const int part = blockIdx.y, K = part == 0 ? args.Kp : args.Kd;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.M() * K) return;
+    const long long m = e / K, ray = m / a.S;
+    const int f = (int)(e - m * K), s = (int)(m - ray * a.S);
+    const RayCtx rc = ray_ctx(a.rays_d, a.params, a.rays_per_param_row, ray, a.n_geo + a.n_app);
+    const float *zray = a.z + (size_t)ray * a.S;
+    bool hit;
+    const float z = depth_of(zray[s], hit);
+    const int K3 = fourier_width(3, part == 0 ? a.pos_freq : a.dir_freq);
+    const bool xyz = f < K3;
+    const float v = fourier_row(xyz ? f : f - K3, xyz ? 3 : (part == 0 ? a.n_geo : a.n_app), [&](int c) -> float {
+        if (!xyz) return blurred_param(rc.pr, part == 0 ? c : a.n_geo + c, a.blur_idx, hit, a.cone, ray, z);     // model.py:88-93, 96-101
+        return part == 0 ? rc.point(a.rays_o[3 * ray + c], c, z) : rc.dir(c);
+    });
+    if (part == 0) for (int i = 0; i < args.n_pos_dst; ++i) args.pos[i].p[(size_t)m * args.pos[i].ld + f] = v;
+    else {
+        args.dir.p[(size_t)m * args.dir.ld + f] = v;
+        if (f == 0) args.dists[(size_t)ray * a.S + s] = sample_dist(zray, s, a.S, z, hit, rc.dn);
+    }
+}
+
+// A narrow head (density: 1 column, colour: 3): out[m][c] = b[c] + sum_k X[m][k] W[k][c], K <= 256.  A wave per row, the row's sum
+// in the fixed order of the lanes' butterfly.
+template <int NOUT>
+__global__ __launch_bounds__(256) void flex_head_kernel(const float *__restrict__ X, int ldx, int K, const float *__restrict__ W, const float *__restrict__ b,
+                                                        float *__restrict__ out, long long M) {
+    const int lane = threadIdx.x & 63;
+    const long long n_waves = (long long)gridDim.x * 4;
+    float w[NOUT][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) w[c][q] = lane + 64 * q < K ? W[(lane + 64 * q) * NOUT + c] : 0.0f;
+    for (long long m = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); m < M; m += n_waves) {
+        float acc[NOUT];
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) acc[c] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float x = lane + 64 * q < K ? X[(size_t)m * ldx + lane + 64 * q] : 0.0f;
+#pragma unroll
+            for (int c = 0; c < NOUT; ++c) acc[c] = fmaf(x, w[c][q], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) { acc[c] = wave_sumf(acc[c]); if (lane == 0) out[(size_t)m * NOUT + c] = acc[c] + b[c]; }
+    }
+}
+// ... its weight gradient over one range of FLEX_SPLIT samples: partial[z][k][c] = sum_m X[m][k] dgrad[m][c0 + c], behind it the bias's
+// partial[z][K][c] = sum_m dgrad[m][c0 + c].  1024 threads = G groups of KK >= K threads (KK a power of two >= 64): group g takes the
+// range's samples g, g + G, ... in ascending order, thread k of it column k; the groups' sums are added in ascending g through LDS -- an order
+// that K and the step's sample count fix.  reduce_batch_kernel adds the ranges up.
+template <int NOUT>
+__global__ __launch_bounds__(1024) void flex_head_wgrad_kernel(const float *__restrict__ X, int ldx, int K, int KK, const float *__restrict__ dgrad, int c0, long long M,
+                                                               float *__restrict__ partial) {
+    __shared__ float red[1024 * NOUT], redb[16 * NOUT];
+    const int k = threadIdx.x & (KK - 1), g = threadIdx.x / KK, G = 1024 / KK;
+    const long long m0 = (long long)blockIdx.x * FLEX_SPLIT, m1 = m0 + FLEX_SPLIT < M ? m0 + FLEX_SPLIT : M;
+    float acc[NOUT], bs[NOUT];
+#pragma unroll
+    for (int c = 0; c < NOUT; ++c) acc[c] = bs[c] = 0.0f;
+#pragma unroll 4
+    for (long long m = m0 + g; m < m1; m += G) {
+        const float x = k < K ? X[(size_t)m * ldx + k] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) { const float d = dgrad[4 * m + c0 + c]; acc[c] = fmaf(x, d, acc[c]); bs[c] += d; }
+    }
+#pragma unroll
+    for (int c = 0; c < NOUT; ++c) { red[threadIdx.x * NOUT + c] = acc[c]; if (k == 0) redb[g * NOUT + c] = bs[c]; }
+    __syncthreads();
+    float *p = partial + (size_t)blockIdx.x * ((size_t)K * NOUT + NOUT);
+    if (g == 0 && k < K) {
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) { float sum = 0.0f; for (int q = 0; q < G; ++q) sum += red[(q * KK + k) * NOUT + c]; p[k * NOUT + c] = sum; }
+    }
+    if (threadIdx.x < NOUT) { float sum = 0.0f; for (int q = 0; q < G; ++q) sum += redb[q * NOUT + threadIdx.x]; p[K * NOUT + threadIdx.x] = sum; }
+}
+// ... and the gradient at its input: G[m][k] = sum_c dgrad[m][c0 + c] W[k][c], kept where act[m][k] > 0 (act NULL: everywhere)
+template <int NOUT>
+__global__ __launch_bounds__(256) void flex_head_dx_kernel(const float *__restrict__ dgrad, int c0, const float *__restrict__ W, int K, const float *__restrict__ act,
+                                                           int ldact, float *__restrict__ G, int ldg, long long M) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * K) return;
+    const long long m = e / K; const int k = (int)(e - m * K);
+    float v = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NOUT; ++c) v = fmaf(dgrad[4 * m + c0 + c], W[k * NOUT + c], v);
+    if (act && !(act[(size_t)m * ldact + k] > 0.0f)) v = 0.0f;
+    G[(size_t)m * ldg + k] = v;
+}
+// The hidden rows of every kernel transposed, once a step: wt[dst + j * hid + r] = w[src + r * out + j] -- the [K][N] operand of
+// dX = dY . W^T (the encoding rows of a layer behind a concatenation take no gradient further and are left out)
+struct FlexTSeg { long long src, dst, first, count; int hid, out; };
+__global__ void flex_transpose_kernel(const float *__restrict__ w, float *__restrict__ wt, const FlexTSeg *__restrict__ seg, int n_seg, long long total) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg[mid].first <= e) lo = mid; else hi = mid - 1; }
+    const FlexTSeg &s = seg[lo];
+    const long long o = e - s.first;
+    if (o >= s.count) return;
+    const int j = (int)(o / s.hid), r = (int)(o - (long long)j * s.hid);
+    wt[s.dst + o] = w[s.src + (size_t)r * s.out + j];
+}
+}   // namespace ntx_train
+namespace {
+using namespace ntx_train;
+// A Dense layer with an activation buffer of its own: trunk 0 .. depth-1, the feature layer, the colour layers, the colour half layer
+// (model.py:104-122).  Its input X is the buffer of the layer in front -- [encoding | hidden] where a concatenation lies between them
+// (a skip: pos_map, model.py:107-108; the feature layer: dir_map, :115) --, its output goes to Y = its own buffer behind the encoding
+// columns of the concatenation that follows it.
+struct FlexLayer {
+    int in = 0, out = 0, enc = 0, src = -1, relu = 0;   // enc: the leading input rows that are an encoding (no gradient further); src: the layer whose output the others are
+    size_t w = 0, b = 0;                                // offsets into the Keras-order blob
+    const float *X = nullptr; int ldx = 0;
+    float *Y = nullptr; int ldy = 0;
+    long long wt = -1;                                  // its transposed hidden rows [out][in - enc] in FlexBackend::wt
+};
+
+inline int pad4(int n) { return (n + 3) & ~3; }
+unsigned flex_skip_mask(const ntx_model_desc *d) {
+    if (d->skip < 0) return 0u;
+    if (d->skip & NTX_SKIP_MASK) return (unsigned)d->skip & (NTX_SKIP_MASK - 1u);
+    return d->skip < 30 ? 1u << d->skip : 0u;
+}
+unsigned flex_trunk_skips(const ntx_model_desc *d) { return flex_skip_mask(d) & ((1u << (d->depth > 1 ? d->depth - 1 : 0)) - 1u); }
+
+struct FlexBackend : Backend {
+    ntx_trainer *t = nullptr;
+    std::vector<FlexLayer> layers;
+    std::vector<int> relu_layers;                       // the oracle's mask order: trunk, colour hidden layers, colour half
+    TLayer rgb{}, alpha{};
+    int last_trunk = 0, half = 0;                       // indices into layers
+    int ldg = 0;
+    float *G[2] = {nullptr, nullptr};                   // the gradient at a layer's output, ping-pong
+    float *wt = nullptr; FlexTSeg *tseg = nullptr; int n_tseg = 0; long long t_total = 0;
+    float *partial = nullptr, *colsum = nullptr;        // [n_split][in * out], [n_split][out] of the layer whose weight gradient is being taken
+    FlexDst pos_dst[FLEX_MAX_DST]; int n_pos_dst = 0; FlexDst dir_dst{};
+    size_t plan(const ntx_model_desc *d, int Kp, int Kd);
+    void place();
+    int forward(const StepRays &r, hipStream_t st) override;
+    int backward(const StepRays &r, hipStream_t st) override;
+    int activation(int layer, int64_t n_samples_total, float *out_host) override;
+};
+
+// the layers of the architecture in forward order with their places in the Keras-order blob (model.layer_table(): trunk, feature, colour
+// hidden layers, colour half, color, alpha); returns the blob's floats
+size_t FlexBackend::plan(const ntx_model_desc *d, int Kp, int Kd) {
+    const int depth = d->depth, w = d->width, cd = d->kind == NTX_MODEL_NERF ? 0 : d->color_depth;
+    const unsigned skips = flex_trunk_skips(d);
+    size_t p = 0;
+    auto add = [&](int in, int out, int enc, int src, int relu) {
+        FlexLayer l; l.in = in; l.out = out; l.enc = enc; l.src = src; l.relu = relu; l.w = p; l.b = p + (size_t)in * out;
+        p += (size_t)in * out + out;
+        layers.push_back(l);
+        if (relu) relu_layers.push_back((int)layers.size() - 1);
+    };
+    for (int i = 0; i < depth; ++i) {
+        const int enc = i == 0 ? Kp : (((skips >> (i - 1)) & 1u) ? Kp : 0);
+        add(i == 0 ? Kp : w + enc, w, enc, i - 1, 1);
+    }
+    last_trunk = depth - 1;
+    add(w, w, 0, depth - 1, 0);                                              // the feature layer: no activation (model.py:114)
+    for (int i = 0; i < cd; ++i) add(i == 0 ? w + Kd : w, w, i == 0 ? Kd : 0, depth + i, 1);
+    add(cd > 0 ? w : w + Kd, w / 2, cd > 0 ? 0 : Kd, depth + cd, 1);         // :122
+    half = (int)layers.size() - 1;
+    rgb = TLayer{w / 2, 3, p, p + (size_t)(w / 2) * 3}; p += (size_t)(w / 2) * 3 + 3;
+    alpha = TLayer{w, 1, p, p + (size_t)w}; p += (size_t)w + 1;
+    return p;
+}
+
+// a buffer per layer, [the encoding of the concatenation behind it | its output], rows padded to 16 bytes; the first layer reads pos_map.
+// Then the gradients' ping-pong, the weight gradients' partial sums and the transposed kernels with their table
+void FlexBackend::place() {
+    DeviceMemory &mem = t->mem;
+    const ntx_model_desc &d = t->desc;
+    const long long M = t->cap;
+    const int Kp = t->Kp, Kd = t->Kd;
+    const unsigned skips = flex_trunk_skips(&d);
+    float *pos = nullptr;
+    mem.alloc(&pos, (size_t)M * pad4(Kp));
+    pos_dst[n_pos_dst++] = FlexDst{pos, pad4(Kp)};
+    std::vector<float *> base(layers.size(), nullptr);
+    size_t most_dw = 1024;                                                 // (the heads' partial sums: at most 128 x 3 + 3 floats a range)
+    for (size_t i = 0; i < layers.size(); ++i) {
+        FlexLayer &l = layers[i];
+        const int front = (int)i < d.depth ? (((skips >> i) & 1u) ? Kp : 0) : ((int)i == d.depth ? Kd : 0);
+        l.ldy = pad4(front + l.out);
+        mem.alloc(&base[i], (size_t)M * l.ldy);
+        l.Y = base[i] ? base[i] + front : nullptr;
+        if ((int)i < d.depth && front) pos_dst[n_pos_dst++] = FlexDst{base[i], l.ldy};
+        if ((int)i == d.depth) dir_dst = FlexDst{base[i], l.ldy};
+        if (i == 0) { l.X = pos; l.ldx = pad4(Kp); }
+        else { l.X = base[l.src]; l.ldx = layers[l.src].ldy; }                              // (the whole row: encoding columns first, as the kernel's rows are)
+        most_dw = std::max(most_dw, (size_t)l.in * l.out);
+    }
+    ldg = pad4(d.width);
+    mem.alloc(&G[0], (size_t)M * ldg); mem.alloc(&G[1], (size_t)M * ldg);
+    const size_t splits = (size_t)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
+    mem.alloc(&partial, splits * most_dw); mem.alloc(&colsum, splits * 256);
+    std::vector<FlexTSeg> segs;
+    long long at = 0;
+    for (size_t i = 1; i < layers.size(); ++i) {
+        FlexLayer &l = layers[i];
+        const int hid = l.in - l.enc;
+        l.wt = at;
+        segs.push_back(FlexTSeg{(long long)(l.w + (size_t)l.enc * l.out), at, at, (long long)hid * l.out, hid, l.out});
+        at += ((long long)hid * l.out + 3) / 4 * 4;
+    }
+    t_total = at; n_tseg = (int)segs.size();
+    mem.alloc(&wt, (size_t)at);
+    mem.upload(&tseg, segs, "segment");
+}
+
+int FlexBackend::forward(const StepRays &r, hipStream_t st) {
+    const long long M = r.M();
+    const float *W = t->w;
+    hipLaunchKernelGGL(flex_transpose_kernel, dim3((unsigned)((t_total + 255) / 256)), dim3(256), 0, st, W, wt, tseg, n_tseg, t_total);
+    {
+        FlexEncodeArgs e{}; e.r = r; e.Kp = t->Kp; e.Kd = t->Kd; e.n_pos_dst = n_pos_dst; e.dir = dir_dst; e.dists = t->dists;
+        for (int i = 0; i < n_pos_dst; ++i) e.pos[i] = pos_dst[i];
+        const long long most = M * std::max(t->Kp, t->Kd);
+        hipLaunchKernelGGL(flex_encode_kernel, dim3((unsigned)((most + 255) / 256), 2), dim3(256), 0, st, e);
+    }
+    for (const FlexLayer &l : layers) {                                      // a contraction per layer, every output kept
+        GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = W + l.w; g.ldb = l.out; g.C = l.Y; g.ldc = l.ldy; g.M = (int)M; g.N = l.out; g.K = l.in; g.bias = W + l.b; g.relu = l.relu;
+        launch_gemm(st, true, g);
+    }
+    const unsigned head_grid = (unsigned)std::min<long long>((M + 3) / 4, (long long)t->cus * 8);
+    const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
+    hipLaunchKernelGGL(flex_head_kernel<1>, dim3(head_grid), dim3(256), 0, st, lt.Y, lt.ldy, lt.out, W + alpha.w, W + alpha.b, t->sigma, M);      // model.py:111
+    hipLaunchKernelGGL(flex_head_kernel<3>, dim3(head_grid), dim3(256), 0, st, lh.Y, lh.ldy, lh.out, W + rgb.w, W + rgb.b, t->raw_rgb, M);        // :123
+    return NTX_OK;
+}
+
+// the way back from the composite's adjoint dgrad [M][4]: per layer, last to first, dW = X^T . dY over ranges of FLEX_SPLIT samples added in
+// ascending order, then dX = (dY . W[hidden rows]^T) where the stored activation in front is > 0
+int FlexBackend::backward(const StepRays &r, hipStream_t st) {
+    const long long M = r.M();
+    const float *W = t->w;
+    const int n_split = (int)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
+    auto reduce = [&](const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
+        ReduceBatch rb{};
+        rb.job[0] = ReduceJob{part, n_split, count, count, 0, t->grad + out, 0};
+        rb.n = 1;
+        if (bias_partial) { rb.job[1] = ReduceJob{bias_partial, n_split, bias_count, bias_count, 0, t->grad + bias_out, (count + 255) / 256 * 256}; rb.n = 2; }
+        launch_reduce(st, rb);
+    };
+    const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
+    const unsigned ew = 256;
+    // the colour head (model.py:123): kernel and bias lie side by side in the blob, as in a range's partial sums
+    auto pow2 = [](int k) { int p = 64; while (p < k) p *= 2; return p; };
+    hipLaunchKernelGGL(flex_head_wgrad_kernel<3>, dim3((unsigned)n_split), dim3(1024), 0, st, lh.Y, lh.ldy, lh.out, pow2(lh.out), t->dgrad, 0, M, partial);
+    reduce(partial, (long long)lh.out * 3 + 3, rgb.w, nullptr, 0, 0);
+    int cur = 0;
+    hipLaunchKernelGGL(flex_head_dx_kernel<3>, dim3((unsigned)((M * lh.out + ew - 1) / ew)), dim3(ew), 0, st, t->dgrad, 0, W + rgb.w, lh.out, lh.Y, lh.ldy, G[cur], ldg, M);
+    for (int i = (int)layers.size() - 1; i >= 0; --i) {
+        const FlexLayer &l = layers[i];
+        const float *dY = G[cur];
+        {   // dW_i and db_i
+            GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldg; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
+            g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
+            launch_gemm(st, false, g, n_split);
+            reduce(partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
+        }
+        if (i == 0) break;                                                   // the inputs are not trained
+        const FlexLayer &s = layers[l.src];
+        float *dX = G[cur ^ 1];
+        int accumulate = 0;
+        if (l.src == last_trunk) {                                           // the density head hangs on the same output (model.py:111): its rank-1 term first
+            hipLaunchKernelGGL(flex_head_wgrad_kernel<1>, dim3((unsigned)n_split), dim3(1024), 0, st, lt.Y, lt.ldy, lt.out, pow2(lt.out), t->dgrad, 3, M, partial);
+            reduce(partial, (long long)lt.out + 1, alpha.w, nullptr, 0, 0);
+            hipLaunchKernelGGL(flex_head_dx_kernel<1>, dim3((unsigned)((M * lt.out + ew - 1) / ew)), dim3(ew), 0, st, t->dgrad, 3, W + alpha.w, lt.out, (const float *)nullptr, 0, dX,
+                               ldg, M);
+            accumulate = 1;
+        }
+        GemmArgs g{}; g.A = dY; g.lda = ldg; g.B = wt + l.wt; g.ldb = l.in - l.enc; g.C = dX; g.ldc = ldg; g.M = (int)M; g.N = l.in - l.enc; g.K = l.out;
+        g.accumulate = accumulate;
+        if (s.relu) { g.mask = s.Y; g.ldmask = s.ldy; }
+        launch_gemm(st, true, g);
+        cur ^= 1;
+    }
+    return NTX_OK;
+}
+
+int FlexBackend::activation(int layer, int64_t n_samples_total, float *out_host) {              // row-major buffers: a strided copy
+    const float *from = nullptr; int width = 0, ld = 0;
+    if (layer >= 0 && layer < (int)relu_layers.size()) { const FlexLayer &l = layers[relu_layers[layer]]; from = l.Y; width = l.out; ld = l.ldy; }
+    else if (layer == 64) { from = t->sigma; width = ld = 1; }
+    else if (layer == 65) { from = t->raw_rgb; width = ld = 3; }
+    else return ntx_set_error(NTX_E_INVALID, "layer %d (0 .. %d: the ReLU layers in the order trunk, colour layers, colour half; 64 the raw density, 65 the raw colour)", layer,
+                              (int)relu_layers.size() - 1);
+    TRAIN_TRY(hipSetDevice(t->device));
+    TRAIN_TRY(hipDeviceSynchronize());
+    TRAIN_TRY(hipMemcpy2D(out_host, (size_t)width * sizeof(float), from, (size_t)ld * sizeof(float), (size_t)width * sizeof(float), (size_t)n_samples_total, hipMemcpyDeviceToHost));
+    return NTX_OK;
+}
+}   // namespace
+namespace ntx_train {
+// the architectures the flex render family takes (nerftex.hip: find_variant) without parameter branches
+int flex_check(const ntx_model_desc *desc, TrainDims *dims) {
+    const bool nerf = desc->kind == NTX_MODEL_NERF;
+    if (desc->kind != NTX_MODEL_PARAMNERF && desc->kind != NTX_MODEL_NERF && desc->kind != NTX_MODEL_PARAMNERF_EX) return ntx_set_error(NTX_E_UNSUPPORTED, "training: model kind %d", desc->kind);
+    if (desc->kind == NTX_MODEL_PARAMNERF_EX && desc->n_geo + desc->n_app > 0 && reinterpret_cast<const ntx_model_desc_ex *>(desc)->param_depth != 0)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: parameter branches (param_depth > 0) render but do not train");
+    if (desc->pos_encoding != NTX_POS_FOURIER || desc->n_pos != 3)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "the layer-by-layer trainer takes Fourier features on n_pos 3 (an IPE model trains in the 8 x 256 / skips [4] / color_depth 1 shape: ntx_trainer_create)");
+    const int n_geo = nerf ? 0 : desc->n_geo, n_app = nerf ? 0 : desc->n_app, cd = nerf ? 0 : desc->color_depth;
+    if (desc->depth < 1 || desc->depth > FLEX_MAX_DEPTH || desc->width < 2 || desc->width > 256 || cd < 0 || cd > FLEX_MAX_COLOR)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: depth %d width %d color_depth %d (built: depth 1..%d, width 2..256, color_depth 0..%d)", desc->depth, desc->width, cd,
+                             FLEX_MAX_DEPTH, FLEX_MAX_COLOR);
+    if ((desc->skip >= 0 && !(desc->skip & NTX_SKIP_MASK) && desc->skip >= 30) || ((flex_skip_mask(desc) >> (desc->depth - 1)) & 1u))
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: a skip behind the last trunk layer (it widens the density head and the feature layer, model.py:107-114) is not built");
+    if (n_geo < 0 || n_geo > 4 || n_app < 0 || n_app > 8 || desc->pos_freq < 0 || desc->pos_freq > 10 || desc->dir_freq < 0 || desc->dir_freq > 4 ||
+        (n_geo + n_app > 0 && (desc->param_freq < 0 || desc->param_freq > 4)))
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: n_parameters [%d,%d] / band counts %d %d %d (built: [g<=4, a<=8], bands <= 10 / 4 / 4)", n_geo, n_app, desc->pos_freq,
+                             desc->dir_freq, desc->param_freq);
+    const int pfq = n_geo + n_app > 0 ? desc->param_freq : 0;
+    dims->desc = *desc; dims->desc.n_geo = n_geo; dims->desc.n_app = n_app; dims->desc.param_freq = pfq; dims->ipe = false;
+    dims->Kp = 3 * (1 + 2 * desc->pos_freq) + n_geo * (1 + 2 * pfq); dims->Kd = 3 * (1 + 2 * desc->dir_freq) + n_app * (1 + 2 * pfq);
+    dims->n_weights = FlexBackend().plan(desc, dims->Kp, dims->Kd);
+    return NTX_OK;
+}
+
+int flex_backend_create(ntx_trainer *t) {
+    FlexBackend *f = new FlexBackend();
+    t->backend = f; f->t = t;
+    f->plan(&t->desc, t->Kp, t->Kd);
+    f->place();
+    return t->mem.rc;
+}
+}   // namespace ntx_train

@@ -1,0 +1,104 @@
+// ntx_trainer.h -- what the units of a training step share on the host: the handle behind ntx_trainer_* (ntx_trainer.hip), the interface of
+// its two backends (ntx_backend_chain.hip: the 8 x 256 chain on ntx_train_device.h's kernels; ntx_backend_flex.hip: any other architecture
+// layer by layer), the owner of its device memory, and the launchers of the kernels more than one unit uses (no relocatable device code: a
+// kernel is launched by a host function of the unit that defines it).
+#pragma once
+#include "nerftex.h"
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <vector>
+
+extern "C" int ntx_set_error(int code, const char *fmt, ...);   // nerftex.hip
+#define TRAIN_TRY(expr)                                                                                  \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return ntx_set_error(NTX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+namespace ntx_train {
+constexpr int MAX_TRAIN_SAMPLES = 1024;                // samples per ray (composite_loss_kernel holds a ray in LDS)
+// Every device allocation of a handle and its backend: what is on the list is freed with the handle, and nothing else is.  The first failure
+// sticks (rc): the allocations behind it are skipped, so a create runs through and looks at rc once.
+struct DeviceMemory {
+    std::vector<void *> ptrs; int rc = NTX_OK;
+    template <class T>
+    int alloc(T **d, size_t n, bool zero = false) {
+        if (rc != NTX_OK) return rc;
+        const size_t bytes = (n ? n : 1) * sizeof(T);
+        if (hipMalloc((void **)d, bytes) != hipSuccess) return rc = ntx_set_error(NTX_E_HIP, "hipMalloc of %zu bytes failed", bytes);
+        ptrs.push_back(*d);
+        if (zero && hipMemset(*d, 0, bytes) != hipSuccess) return rc = ntx_set_error(NTX_E_HIP, "hipMemset failed");
+        return rc;
+    }
+    template <class T>
+    int upload(T **d, const std::vector<T> &host, const char *what) {      // a table the kernels read
+        if (alloc(d, host.size()) == NTX_OK && hipMemcpy(*d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+            rc = ntx_set_error(NTX_E_HIP, "%s table upload failed", what);
+        return rc;
+    }
+    ~DeviceMemory() { for (void *p : ptrs) (void)hipFree(p); }
+};
+
+// the rays of one step and the model's encodings, as the backends' encoders take them (host and device)
+struct StepRays {
+    const float *rays_o, *rays_d, *z, *params, *cone; long long rays_per_param_row, n_rays; int S, blur_idx, n_geo, n_app, pos_freq, dir_freq, param_freq;
+    __host__ __device__ long long M() const { return n_rays * S; }
+    int n_blocks() const { return (int)((M() + 31) / 32); }       // blocks of 32 samples
+};
+// The network between the encoded rays and the composite.  forward leaves sigma, raw_rgb and dists in the handle's buffers and keeps what the
+// way back needs; backward takes the handle's dgrad (and its O-layout copy dhead) to the handle's grad.
+struct Backend {
+    virtual ~Backend() {}                                                            // (its device buffers are on the handle's list)
+    virtual int forward(const StepRays &r, hipStream_t st) = 0;
+    virtual int backward(const StepRays &r, hipStream_t st) = 0;
+    virtual int activation(int layer, int64_t n_samples_total, float *out_host) = 0;   // ntx_trainer_activation, the arguments checked
+};
+// what an entry's architecture check makes of a descriptor
+struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; };
+struct TLayer { int in, out; size_t w, b; };      // offsets into the Keras-order blob (kernel [in][out], then bias)
+}   // namespace ntx_train
+
+struct ntx_trainer {
+    int device = 0, cus = 256;
+    ntx_model_desc desc{};
+    int Kp = 0, Kd = 0, P = 0;                 // features of pos_map / dir_map, parameters the model sees
+    bool ipe = false; size_t n_weights = 0;    // ipe: an IntegratedPositionalEncoding model, a MipRenderer step
+    long long cap = 0, cap_blocks = 0, cap_rays = 0;   // samples (blocks of 32 samples, rays) the buffers hold
+    float *w = nullptr, *grad = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+    float *stash = nullptr;                    // a second gradient (ntx_trainer_stash_gradients)
+    float *sigma = nullptr, *raw_rgb = nullptr, *z = nullptr, *dists = nullptr, *noise = nullptr;
+    float *dgrad = nullptr, *dhead = nullptr;  // the composite's adjoint [M][4], and the same as one O-layout tile per block (the chain's narrow heads' dY)
+    float *color = nullptr, *alpha_out = nullptr, *ray_loss = nullptr, *loss = nullptr;
+    float *weights_out = nullptr;              // caller's [N][S] buffer for the composite's weights of the next steps, or NULL
+    long long adam_iterations = 0;
+    ntx_train::Backend *backend = nullptr;
+    ntx_train::DeviceMemory mem;               // (destroyed after the body below has run)
+    ~ntx_trainer() { (void)hipSetDevice(device); delete backend; }
+};
+namespace ntx_train {
+// ntx_backend_chain.hip / ntx_backend_flex.hip: the entry's architecture check (no device is asked for), and the backend of a handle whose
+// common buffers exist (allocations go through t->mem; the caller looks at t->mem.rc)
+int chain_check(const ntx_model_desc *desc, TrainDims *dims);
+int chain_backend_create(ntx_trainer *t);
+int flex_check(const ntx_model_desc *desc, TrainDims *dims);
+int flex_backend_create(ntx_trainer *t);
+// ntx_gemm.hip: C[i][j] = sum_p A'(i, p) B[p * ldb + j], A'(i, p) = a_kcontig ? A[i * lda + p] : A[p * lda + i]
+struct GemmArgs {
+    const float *A; int lda; const float *B; int ldb; float *C; int ldc;
+    int M, N, K;
+    const float *bias;               // NULL or [N]: added to every row
+    const float *mask; int ldmask;   // NULL, or C[i][j] is kept only where mask[i * ldmask + j] > 0 (the ReLU of a stored activation)
+    int relu, accumulate;            // C = max(C, 0);  C += what was there
+    int k_chunk; long long split_stride;   // blockIdx.z = z covers p in [z * k_chunk, (z + 1) * k_chunk) and writes to C + z * split_stride
+    float *colsum;                   // NULL, or [n_split][N]: the column sums of B over each split's rows (the bias gradient rides along with dW)
+    int aligned;                     // every row of A and B starts on a 16-byte boundary (the launcher's)
+};
+// n_split = 1: the whole of K in one range (k_chunk = K); more: the dW form, the caller's k_chunk and split_stride.  Any M: 65 535 row tiles a launch
+void launch_gemm(hipStream_t st, bool a_kcontig, GemmArgs g, int n_split = 1);
+// ntx_trainer.hip: out[e] = sum_z partial[z][e] (+ the second half of a bias's pair), z ascending: the fixed order that makes a step
+// reproducible.  Several results in one launch; a job's elements are numbered from first (multiples of 256: a block belongs to one job)
+constexpr int MAX_REDUCE_BATCH = 32;
+struct ReduceJob { const float *partial; int n_split; long long stride, count, pair; float *out; long long first; };   // pair > 0: element e of a split is partial[e] + partial[pair + e]
+struct ReduceBatch { ReduceJob job[MAX_REDUCE_BATCH]; int n; };
+void launch_reduce(hipStream_t st, const ReduceBatch &b);
+__device__ __forceinline__ float wave_sumf(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+}   // namespace ntx_train

@@ -1,0 +1,380 @@
+// ntx_trainer.hip -- one training step of the reference on the GPU: network/train.py:49-70 (GradientTape over Renderer.__call__, a loss of
+// network/loss.py:6-59, Adam under ExponentialDecay).  This file is what every architecture shares: the handle behind ntx_trainer_* and its
+// create, the step's skeleton (depths, noise, the backend's forward, composite + loss, the backend's backward), and the kernels around the
+// network: composite_loss_kernel (renderer.py:170-213 per ray, the ray's term of the loss and the adjoint of both), reduce_batch_kernel (the
+// weight gradients' partial sums added in a fixed order: a step is bit-reproducible), adam_kernel (train.py:49-52).
+// The network between the encoded rays and the composite is a backend's (ntx_trainer.h): the 8 x 256 chain of ntx_backend_chain.hip behind
+// ntx_trainer_create, the layer-by-layer step of ntx_backend_flex.hip behind ntx_trainer_create_flex.  Inference fuses the whole network into
+// one kernel because nothing of it has to survive (ntx_device.h); a training step has to keep every layer's activations for the weight
+// gradients, and with 288 GB of HBM they are simply stored, once each.  Everything is float32 with float32 accumulation, like the
+// reference's TensorFlow graph.  gfx950 only.
+#include <cmath>
+#include "ntx_trainer.h"
+#include "ntx_encode.h"   // o_index
+#include "ntx_device.h"   // f32x4
+namespace ntx_train {
+using ntx::f32x4;
+__global__ void reduce_batch_kernel(ReduceBatch b) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    int j = 0;
+    while (j + 1 < b.n && g >= b.job[j + 1].first) ++j;
+    const ReduceJob &r = b.job[j];
+    const long long e = g - r.first;
+    if (e >= r.count) return;
+    // four running sums over z = 0, 4, 8 ... / 1, 5, ... / ..., combined at the end: a fixed order, four loads in flight
+    float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto at = [&](int z) { const float *p = r.partial + (size_t)z * r.stride + e; return r.pair > 0 ? p[0] + p[r.pair] : p[0]; };
+    int z = 0;
+    for (; z + 4 <= r.n_split; z += 4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s4[q] += at(z + q);
+    }
+    for (int q = 0; z < r.n_split; ++z, ++q) s4[q] += at(z);
+    r.out[e] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+}
+void launch_reduce(hipStream_t st, const ReduceBatch &b) {
+    const long long total = b.job[b.n - 1].first + (b.job[b.n - 1].count + 255) / 256 * 256;
+    hipLaunchKernelGGL(reduce_batch_kernel, dim3((unsigned)(total / 256)), dim3(256), 0, st, b);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// map_model_output (renderer.py:170-213) per ray, the ray's terms of the loss (loss.py: both losses are means over the rays, so a ray's
+// gradient needs nothing of the others) and the adjoint of both; wave per ray, lane l holds samples l, l + 64, ...
+// ---------------------------------------------------------------------------------------------------------------------------
+struct CompositeArgs {
+    const float *raw_rgb, *sigma, *dists;      // [N][S][3], [N][S], [N][S]
+    const float *noise;                        // NULL, or [N][S]: raw_noise_std * N(0,1), added to the density before its ReLU (renderer.py:190-195)
+    int n_rays, S, map_exr, composite_bkgd; float bkgd[3];
+    const float *color_true, *alpha_true;
+    int kind, loss_fn, alpha_loss_fn, filter_color_loss, use_hard_mask; float gamma;
+    float *color, *alpha, *ray_loss;           // [N][3], [N], [N]: the predictions and each ray's share of the loss
+    float *weights;                            // NULL, or [N][S]: the composite's weights a_i T_i (what the importance sampler takes, renderer.py:127-128)
+    float *dgrad;                              // [M][4]: dL/d raw rgb, dL/d sigma per sample (the way back starts from these)
+    float *dhead;                              // the same as one O-layout tile per block of 32 samples (rows 0-2, 3): the narrow heads' dY
+    long long M;
+};
+__device__ __forceinline__ float rgb_of(float raw, int map_exr) {
+    if (map_exr) return raw > 0.0f ? raw + 1.0f : expf(raw);                                   // elu + 1 (:184-185)
+    return 1.0f / (1.0f + expf(-raw));                                                         // sigmoid (:187)
+}
+__device__ __forceinline__ void loss_term(int fn, float t, float p, float inv_n, float &value, float &grad) {
+    if (fn == NTX_LOSS_MSE) { const float e = t - p; value = e * e * inv_n; grad = -2.0f * e * inv_n; }          // loss.py:51-54
+    else {                                                                                                        // smape, eps 1e-2 (:56-59)
+        const float e = t - p, den = (t + p) + 1e-2f, ae = fabsf(e);
+        const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
+        value = ae / den * inv_n; grad = (-sgn / den - ae / (den * den)) * inv_n;
+    }
+}
+__device__ __forceinline__ size_t dhead_at(long long m, int row) { return o_index(m >> 5, 1, row, (int)(m & 31)); }
+__global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0) {                                 // the tail of the last block of 32 samples: no gradient
+        const long long end = (a.M + 31) / 32 * 32;
+        for (long long m = a.M + threadIdx.x; m < end; m += 256)
+            for (int r = 0; r < 4; ++r) a.dhead[dhead_at(m, r)] = 0.0f;
+    }
+    const int ray = blockIdx.x * 4 + wave;
+    if (ray >= a.n_rays) return;
+    const int S = a.S;
+    const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S, *rr = a.raw_rgb + (size_t)ray * S * 3;
+    const float *nz = a.noise ? a.noise + (size_t)ray * S : nullptr;
+    // el[s] = exp(-relu(sigma) dist): a_s = 1 - el[s] (:195), and the factor of the running product, (1 - a_s) + 1e-10 (:198), is taken as
+    // el[s] + 1e-10 -- the value of the reference's expression without the float32 round trip through 1 - (1 - e), which on a saturated sample
+    // (e ~ 1e-6) leaves 1 - a with two digits: the ray's transmittance, and with it every gradient behind the sample, would carry that error
+    float *el = sh_a[wave], *T = sh_T[wave];
+    for (int s = lane; s < S; s += 64) { const float v = nz ? sg[s] + nz[s] : sg[s]; const float r = v > 0.0f ? v : 0.0f; el[s] = expf(-r * ds[s]); }    // :190-195
+    __builtin_amdgcn_wave_barrier();
+    // exclusive running product of (1 - a) + 1e-10, sequential like tf.math.cumprod (:198): chunks of 64 with a carry
+    float carry = 1.0f;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        float f = s < S ? el[s] + 1e-10f : 1.0f, incl = f;
+        for (int o = 1; o < 64; o <<= 1) { const float w = __shfl_up(incl, o); if (lane >= o) incl *= w; }
+        float excl = __shfl_up(incl, 1);
+        if (lane == 0) excl = 1.0f;
+        if (s < S) T[s] = carry * excl;
+        carry *= __shfl(incl, 63);
+    }
+    __builtin_amdgcn_wave_barrier();
+    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, A = 0.0f;
+    for (int s = lane; s < S; s += 64) {
+        const float w = (1.0f - el[s]) * T[s];
+        c0 += w * rgb_of(rr[3 * s], a.map_exr); c1 += w * rgb_of(rr[3 * s + 1], a.map_exr); c2 += w * rgb_of(rr[3 * s + 2], a.map_exr);
+        A += w;
+        if (a.weights) a.weights[(size_t)ray * S + s] = w;
+    }
+    c0 = wave_sumf(c0); c1 = wave_sumf(c1); c2 = wave_sumf(c2); A = wave_sumf(A);
+    if (a.composite_bkgd) { c0 += (1.0f - A) * a.bkgd[0]; c1 += (1.0f - A) * a.bkgd[1]; c2 += (1.0f - A) * a.bkgd[2]; }   // :210-211
+    // the ray's terms of the loss and their derivatives (loss.py:6-49)
+    const float cp[3] = {c0, c1, c2};
+    float dC[3], dA = 0.0f, total = 0.0f;
+    {
+        const float inv_c = 1.0f / (float)(a.n_rays * 3), inv_a = 1.0f / (float)a.n_rays;
+        float mask = 1.0f;
+        if (a.kind == NTX_LOSS_ALPHA && a.filter_color_loss) mask = a.use_hard_mask ? (a.alpha_true[ray] > 0.0f ? 1.0f : 0.0f) : a.alpha_true[ray];   // :29-35
+        for (int c = 0; c < 3; ++c) {
+            float v, gr;
+            loss_term(a.loss_fn, a.color_true[3 * ray + c] * mask, cp[c] * mask, inv_c, v, gr);
+            total += v; dC[c] = gr * mask;
+        }
+        if (a.kind == NTX_LOSS_ALPHA) { float v; loss_term(a.alpha_loss_fn, a.alpha_true[ray], A, inv_a, v, dA); total += a.gamma * v; dA *= a.gamma; }   // :38
+    }
+    if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; a.ray_loss[ray] = total; }
+    // adjoint.  C = sum w rgb (+ (1 - A) bkgd), A = sum w, w_i = a_i T_i, T_i = prod_{j<i} f_j, f_j = (1 - a_j) + 1e-10.  With
+    // dL/dw_k = c_k + dA' (c_k = dC . rgb_k, dA' = dA - dC . bkgd):
+    //     dL/da_i = T_i (dA' Z_i + (c_i - V_i)),
+    //     V_i = sum_{k>i} c_k a_k prod_{i<j<k} f_j   (the colour composited behind sample i, along dC):   V_{i-1} = c_i a_i + f_i V_i,  V_{S-1} = 0
+    //     Z_i = 1 - sum_{k>i} a_k prod_{i<j<k} f_j   (what is left of the ray behind sample i):            Z_{i-1} = f_i Z_i - 1e-10,   Z_{S-1} = 1
+    // Nothing is divided and the opacity term is never formed as a difference of two sums.  tf.math.cumprod's own gradient
+    // (TF 2.4 math_grad.py _CumprodGrad: cumsum(out * grad, reverse) / x) is the same derivative as a quotient by f_i, which on a saturated
+    // sample (f_i -> 1e-10) loses the digits the forward product kept, and "dA' (1 - sum)" loses them again when the ray saturates BEHIND
+    // sample i (round 5's kernel did both: profiles/r05/soak_train_seed3.txt, case 297).
+    // A chunk of 64 samples is a suffix scan of the affine maps X -> b_i + f_i X (composed pairwise), carried from chunk to chunk back to front.
+    if (a.composite_bkgd) dA -= (dC[0] * a.bkgd[0] + dC[1] * a.bkgd[1]) + dC[2] * a.bkgd[2];
+    float Z_carry = 1.0f, V_carry = 0.0f;                  // Z, V of the last sample of the current chunk (nothing lies behind the ray's end)
+    for (int s0 = ((S - 1) / 64) * 64; s0 >= 0; s0 -= 64) {
+        const int s = s0 + lane;
+        float cs = 0.0f, rgb[3] = {0.0f, 0.0f, 0.0f}, e = 1.0f;
+        float F = 1.0f, Bz = 0.0f, Bv = 0.0f;              // the identity for the lanes past the ray's end
+        if (s < S) {
+            e = el[s];
+            for (int c = 0; c < 3; ++c) rgb[c] = rgb_of(rr[3 * s + c], a.map_exr);
+            cs = (dC[0] * rgb[0] + dC[1] * rgb[1]) + dC[2] * rgb[2];
+            F = e + 1e-10f; Bz = -1e-10f; Bv = cs * (1.0f - e);
+        }
+        // inclusive suffix composition: lane l ends with the maps of samples l .. 63 of the chunk composed, X_{l-1} = B + F X_63
+        for (int o = 1; o < 64; o <<= 1) {
+            const float Fo = __shfl_down(F, o), Bzo = __shfl_down(Bz, o), Bvo = __shfl_down(Bv, o);
+            if (lane + o < 64) { Bz = fmaf(F, Bzo, Bz); Bv = fmaf(F, Bvo, Bv); F *= Fo; }
+        }
+        float Fn = __shfl_down(F, 1), Bzn = __shfl_down(Bz, 1), Bvn = __shfl_down(Bv, 1);   // the lanes strictly behind this one
+        if (lane == 63) { Fn = 1.0f; Bzn = 0.0f; Bvn = 0.0f; }
+        const float Z = fmaf(Fn, Z_carry, Bzn), V = fmaf(Fn, V_carry, Bvn);
+        if (s < S) {
+            const float w = (1.0f - e) * T[s];
+            const float d_a = T[s] * fmaf(dA, Z, cs - V);
+            const float sig = nz ? sg[s] + nz[s] : sg[s];
+            float gr[4];
+            for (int c = 0; c < 3; ++c) {
+                const float raw = rr[3 * s + c];
+                const float drgb = a.map_exr ? (raw > 0.0f ? 1.0f : expf(raw)) : rgb[c] * (1.0f - rgb[c]);
+                gr[c] = w * dC[c] * drgb;
+            }
+            gr[3] = sig > 0.0f ? d_a * ds[s] * e : 0.0f;                                       // da/dsigma = dist exp(-sigma dist)
+            const long long m = (long long)ray * S + s;
+            *reinterpret_cast<f32x4 *>(a.dgrad + 4 * m) = f32x4{gr[0], gr[1], gr[2], gr[3]};
+            for (int r = 0; r < 4; ++r) a.dhead[dhead_at(m, r)] = gr[r];
+        }
+        const float F0 = __shfl(F, 0);
+        Z_carry = fmaf(F0, Z_carry, __shfl(Bz, 0)); V_carry = fmaf(F0, V_carry, __shfl(Bv, 0));
+    }
+}
+// the loss: the rays' terms added up by one workgroup in a fixed order
+__global__ __launch_bounds__(1024) void loss_sum_kernel(const float *__restrict__ ray_loss, int n_rays, float *__restrict__ loss) {
+    __shared__ float red[1024];
+    float total = 0.0f;
+    for (int r = threadIdx.x; r < n_rays; r += blockDim.x) total += ray_loss[r];
+    red[threadIdx.x] = total;
+    __syncthreads();
+    for (int o = blockDim.x / 2; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) *loss = red[0];
+}
+
+// tf.keras.optimizers.Adam (TF 2.4, non-amsgrad): m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2;
+// w -= lr sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps), t = iterations + 1; lr from ExponentialDecay (train.py:49-52) on the host
+__global__ void adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long long n, float lr_t, float b1,
+                            float b2, float eps) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float ge = g[e];
+    const float me = m[e] + (ge - m[e]) * (1.0f - b1);
+    const float ve = v[e] + (ge * ge - v[e]) * (1.0f - b2);
+    m[e] = me; v[e] = ve;
+    w[e] = w[e] - (me * lr_t) / (sqrtf(ve) + eps);
+}
+}   // namespace ntx_train
+
+using namespace ntx_train;
+// Both create entries: the architecture check first (trainer_class_for in train.py asks with max_rays = 0 and counts on NTX_E_UNSUPPORTED
+// before NTX_E_INVALID, and on no device being asked for before either), then the sizes, the device, the handle with the buffers and weights
+// every backend needs, and the backend.
+static int trainer_create(bool flex, const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
+    if (!out) return ntx_set_error(NTX_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!desc || !weights) return ntx_set_error(NTX_E_INVALID, "desc / weights is NULL");
+    TrainDims dm{};
+    int rc = flex ? flex_check(desc, &dm) : chain_check(desc, &dm);
+    if (rc != NTX_OK) return rc;
+    if (max_rays < 1 || max_samples_per_ray < 2 || max_samples_per_ray > MAX_TRAIN_SAMPLES || max_rays * (int64_t)max_samples_per_ray > (int64_t)1 << 30)
+        return ntx_set_error(NTX_E_INVALID, "max_rays / max_samples_per_ray out of range (samples per ray <= %d)", MAX_TRAIN_SAMPLES);
+    const size_t p = dm.n_weights;
+    auto count_ok = [&]() { return n_floats == p ? NTX_OK : ntx_set_error(NTX_E_INVALID, "weights: %zu floats, the model has %zu", n_floats, p); };
+    if (flex && (rc = count_ok()) != NTX_OK) return rc;          // the layer-by-layer entry says so before it asks for a device, the chain's after
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ntx_set_error(NTX_E_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return ntx_set_error(NTX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
+    if (!flex && (rc = count_ok()) != NTX_OK) return rc;
+    ntx_trainer *t = new ntx_trainer();
+    t->device = device; t->desc = dm.desc; t->ipe = dm.ipe; t->P = dm.desc.n_geo + dm.desc.n_app; t->Kp = dm.Kp; t->Kd = dm.Kd; t->n_weights = p;
+    const long long M = (long long)max_rays * max_samples_per_ray, NB = (M + 31) / 32;
+    t->cap = M; t->cap_rays = max_rays; t->cap_blocks = NB;
+    DeviceMemory &mem = t->mem;
+    if (hipSetDevice(device) != hipSuccess) mem.rc = ntx_set_error(NTX_E_HIP, "hipSetDevice(%d) failed", device);
+    else { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) t->cus = n; }
+    mem.alloc(&t->w, p); mem.alloc(&t->grad, p, true); mem.alloc(&t->adam_m, p, true); mem.alloc(&t->adam_v, p, true);
+    mem.alloc(&t->sigma, (size_t)M); mem.alloc(&t->raw_rgb, (size_t)M * 3); mem.alloc(&t->dists, (size_t)M); mem.alloc(&t->noise, (size_t)M);
+    mem.alloc(&t->z, (size_t)(M + max_rays));                                                   // (a mip step's S + 1 segment edges a ray)
+    mem.alloc(&t->dgrad, (size_t)NB * 32 * 4); mem.alloc(&t->dhead, (size_t)NB * 1024, true);   // rows 4 .. 31 of the heads' dY tile stay zero
+    mem.alloc(&t->color, (size_t)max_rays * 3); mem.alloc(&t->alpha_out, (size_t)max_rays); mem.alloc(&t->ray_loss, (size_t)max_rays); mem.alloc(&t->loss, 1);
+    if (mem.rc == NTX_OK && hipMemcpy(t->w, weights, p * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) mem.rc = ntx_set_error(NTX_E_HIP, "weight upload failed");
+    rc = flex ? flex_backend_create(t) : chain_backend_create(t);
+    if (rc != NTX_OK) { delete t; return rc; }                                                  // (frees what was made)
+    *out = t;
+    return NTX_OK;
+}
+
+extern "C" {
+int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
+    return trainer_create(false, desc, weights, n_floats, device, max_rays, max_samples_per_ray, out);
+}
+
+int ntx_trainer_create_flex(const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
+    return trainer_create(true, desc, weights, n_floats, device, max_rays, max_samples_per_ray, out);
+}
+int ntx_trainer_destroy(ntx_trainer *t) { delete t; return NTX_OK; }
+size_t ntx_trainer_weight_count(const ntx_trainer *t) { return t ? t->n_weights : 0; }
+
+// one of the handle's four vectors to the host or from it
+static int trainer_copy(ntx_trainer *t, int what, float *to_host, const float *from_host, size_t n_floats) {
+    if (!t || (!to_host && !from_host)) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (n_floats != t->n_weights) return ntx_set_error(NTX_E_INVALID, "%zu floats %s, the model has %zu", n_floats, to_host ? "asked" : "given", t->n_weights);
+    float *v = what == NTX_TRAINER_WEIGHTS ? t->w : what == NTX_TRAINER_GRADIENTS ? t->grad : what == NTX_TRAINER_ADAM_M ? t->adam_m : what == NTX_TRAINER_ADAM_V ? t->adam_v : nullptr;
+    if (!v) return ntx_set_error(NTX_E_INVALID, "what = %d", what);
+    TRAIN_TRY(hipSetDevice(t->device));
+    TRAIN_TRY(hipDeviceSynchronize());
+    TRAIN_TRY(to_host ? hipMemcpy(to_host, v, n_floats * sizeof(float), hipMemcpyDeviceToHost) : hipMemcpy(v, from_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    return NTX_OK;
+}
+int ntx_trainer_get(ntx_trainer *t, int what, float *out_host, size_t n_floats) { return trainer_copy(t, what, out_host, nullptr, n_floats); }
+int ntx_trainer_set(ntx_trainer *t, int what, const float *values_host, size_t n_floats) { return trainer_copy(t, what, nullptr, values_host, n_floats); }
+int ntx_trainer_set_weights(ntx_trainer *t, const float *weights_host, size_t n_floats) { return ntx_trainer_set(t, NTX_TRAINER_WEIGHTS, weights_host, n_floats); }
+
+int ntx_trainer_activation(ntx_trainer *t, int layer, int64_t n_samples_total, float *out_host) {
+    if (!t || !out_host) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (n_samples_total < 1 || n_samples_total > t->cap) return ntx_set_error(NTX_E_INVALID, "n_samples_total out of range");
+    return t->backend->activation(layer, n_samples_total, out_host);
+}
+
+int ntx_trainer_set_iterations(ntx_trainer *t, int64_t iterations) {
+    if (!t || iterations < 0) return ntx_set_error(NTX_E_INVALID, "trainer is NULL or iterations < 0");
+    t->adam_iterations = iterations;
+    return NTX_OK;
+}
+
+int ntx_trainer_composite_weights(ntx_trainer *t, float *weights_dev) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    if (t->ipe && weights_dev) return ntx_set_error(NTX_E_UNSUPPORTED, "an IPE trainer has no importance pass (MipRenderer: renderer.py:403-404)");
+    t->weights_out = weights_dev;
+    return NTX_OK;
+}
+namespace ntx_train {
+__global__ void add_kernel(float *__restrict__ dst, const float *__restrict__ src, long long n) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) dst[e] += src[e];
+}
+}   // namespace ntx_train
+
+int ntx_trainer_stash_gradients(ntx_trainer *t, int op, ntx_stream stream) {
+    if (!t || (op != 0 && op != 1)) return ntx_set_error(NTX_E_INVALID, "trainer is NULL or op is not 0 (keep) / 1 (add back)");
+    TRAIN_TRY(hipSetDevice(t->device));
+    if (!t->stash) {
+        if (op == 1) return ntx_set_error(NTX_E_INVALID, "no gradient was kept");
+        if (t->mem.alloc(&t->stash, t->n_weights) != NTX_OK) return t->mem.rc;
+    }
+    if (op == 0) TRAIN_TRY(hipMemcpyAsync(t->stash, t->grad, t->n_weights * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else hipLaunchKernelGGL(ntx_train::add_kernel, dim3((unsigned)((t->n_weights + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->grad, t->stash, (long long)t->n_weights);
+    TRAIN_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+int ntx_trainer_device_weights(ntx_trainer *t, const float **weights_dev) {
+    if (!t || !weights_dev) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    *weights_dev = t->w;
+    return NTX_OK;
+}
+
+int ntx_trainer_allreduce_gradients(ntx_trainer *t, ntx_comm *comm, ntx_stream stream) {
+    if (!t || !comm) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    return ntx_allreduce_mean_f32(comm, t->grad, t->n_weights, stream);
+}
+
+int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
+                             const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
+                             const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,
+                             float *color_pred, float *alpha_pred, float *loss_out, ntx_stream stream) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    const int P_in = t->P + (t->ipe ? 1 : 0);                                               // the MipRenderer's rows still hold the blur parameter
+    if (!rays_o || !rays_d || (!tnear_far && !z_vals) || !color_true || !loss || (P_in > 0 && !params)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (n_rays < 1 || n_rays > t->cap_rays || n_samples < 2 || (long long)n_rays * n_samples > t->cap) return ntx_set_error(NTX_E_INVALID, "n_rays x n_samples beyond what the trainer was created for");
+    if (n_samples > MAX_TRAIN_SAMPLES) return ntx_set_error(NTX_E_INVALID, "n_samples > %d", MAX_TRAIN_SAMPLES);
+    if (blur_idx >= P_in || (blur_idx >= 0 && !cone_scale) || (t->ipe && blur_idx < 0)) return ntx_set_error(NTX_E_INVALID, "bad blur_idx / cone_scale");
+    if (loss->size < sizeof(ntx_loss_desc) || (loss->kind != NTX_LOSS_NERF && loss->kind != NTX_LOSS_ALPHA) || (loss->loss_fn != NTX_LOSS_MSE && loss->loss_fn != NTX_LOSS_SMAPE) ||
+        (loss->alpha_loss_fn != NTX_LOSS_MSE && loss->alpha_loss_fn != NTX_LOSS_SMAPE))
+        return ntx_set_error(NTX_E_INVALID, "bad ntx_loss_desc");
+    if (loss->kind == NTX_LOSS_ALPHA && !alpha_true) return ntx_set_error(NTX_E_INVALID, "AlphaLoss needs alpha_true");
+    if (rays_per_param_row < 1) rays_per_param_row = 1;
+    TRAIN_TRY(hipSetDevice(t->device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)n_rays * n_samples;
+    const int S = n_samples;
+    const float *z = z_vals;                                                                    // [N][S], or the S + 1 segment edges of a mip step
+    if (!z) {
+        int rc = ntx_sample_depths(tnear_far, n_rays, t->ipe ? S + 1 : S, flags & NTX_FLAG_PERTURB, perturb_seed, opts, t->z, stream);     // renderer.py:101-111, 374-383
+        if (rc != NTX_OK) return rc;
+        z = t->z;
+    }
+    const float *noise = nullptr;
+    if (flags & NTX_FLAG_RAW_NOISE) {                                                           // renderer.py:190-192
+        int rc = ntx_sample_noise(n_rays, S, perturb_seed, opts, t->noise, stream);
+        if (rc != NTX_OK) return rc;
+        noise = t->noise;
+    }
+    const ntx_model_desc &d = t->desc;
+    const StepRays rays{rays_o, rays_d, z, params, cone_scale, rays_per_param_row, n_rays, S, blur_idx, d.n_geo, d.n_app, d.pos_freq, d.dir_freq, d.param_freq};
+    int rc = t->backend->forward(rays, st);                                                     // every activation kept
+    if (rc != NTX_OK) return rc;
+    // ---- the composite, the loss (loss.py) and their adjoint ------------------------------------------------------------------------
+    CompositeArgs c{};
+    c.raw_rgb = t->raw_rgb; c.sigma = t->sigma; c.dists = t->dists; c.noise = noise; c.n_rays = (int)n_rays; c.S = S; c.map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0;
+    c.composite_bkgd = (flags & NTX_FLAG_COMPOSITE_BKGD) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) c.bkgd[k] = bkgd ? bkgd[k] : 1.0f;
+    c.color_true = color_true; c.alpha_true = alpha_true; c.kind = loss->kind; c.loss_fn = loss->loss_fn; c.alpha_loss_fn = loss->alpha_loss_fn;
+    c.filter_color_loss = loss->filter_color_loss; c.use_hard_mask = loss->use_hard_mask; c.gamma = loss->gamma;
+    c.weights = t->weights_out;
+    c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.ray_loss = t->ray_loss; c.dgrad = t->dgrad; c.dhead = t->dhead; c.M = M;
+    hipLaunchKernelGGL(composite_loss_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, t->ray_loss, (int)n_rays, loss_out ? loss_out : t->loss);
+    rc = t->backend->backward(rays, st);
+    if (rc != NTX_OK) return rc;
+    TRAIN_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+int ntx_trainer_adam_step(ntx_trainer *t, float lrate, float lrate_decay_steps, float lrate_decay_rate, float beta_1, float beta_2, float epsilon, ntx_stream stream) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    TRAIN_TRY(hipSetDevice(t->device));
+    const double step = (double)t->adam_iterations;
+    double lr = lrate;
+    if (lrate_decay_steps > 0) lr = (double)lrate * std::pow((double)lrate_decay_rate, step / (double)lrate_decay_steps);      // ExponentialDecay, staircase off
+    const double tt = step + 1.0;
+    const float lr_t = (float)((double)(float)lr * std::sqrt(1.0 - std::pow((double)beta_2, tt)) / (1.0 - std::pow((double)beta_1, tt)));
+    hipLaunchKernelGGL(ntx_train::adam_kernel, dim3((unsigned)((t->n_weights + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->w, t->grad, t->adam_m, t->adam_v,
+                       (long long)t->n_weights, lr_t, beta_1, beta_2, epsilon);
+    t->adam_iterations += 1;
+    TRAIN_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+int64_t ntx_trainer_iterations(const ntx_trainer *t) { return t ? t->adam_iterations : -1; }
+}   // extern "C"

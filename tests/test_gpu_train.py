@@ -248,7 +248,7 @@ def test_saturated_rays_of_soak_seed_3_case_297():
     """The batch tools/dev/soak_train.py --seed 3 drew as case 297 (profiles/r05/soak_train_seed3.txt): grass_filtered, 2 rays x 5 samples, both
     saturated (alpha_pred 1.0 and 0.9999975) against alpha targets of 0, alpha_mse_soft over a background, jittered depths.  The whole gradient
     hangs on a transmittance of 2.5e-6.  Round 5's composite adjoint divided a suffix sum by (1 - a_i) + 1e-10 and was 4.6e-3 .. 7.2e-3 per
-    layer from float64 here; the division-free reverse scan (csrc/ntx_train.hip composite_loss_kernel) is held to the plain 1e-4."""
+    layer from float64 here; the division-free reverse scan (csrc/ntx_trainer.hip composite_loss_kernel) is held to the plain 1e-4."""
     model, spec, wts = make_model((2, 3), dense_media=True)
     e = step_errors(model, spec, wts, "grass_filtered", 2, 5, "alpha_mse_soft", perturb=True, bkgd=True, seed=840038945, batch_seed=996772, cap=45)
     assert e["alpha_pred"].min() > 0.99999, e["alpha_pred"]                      # the case is the saturated one

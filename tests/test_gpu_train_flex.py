@@ -57,7 +57,7 @@ def test_gradients_of_every_layer_match_float64_autograd(arch_id, npar, kind, ar
 
 @pytest.mark.parametrize("n,S", [(300, 70), (41, 70)])
 def test_the_weight_gradients_split(n, S):
-    """dW = X^T . dY is summed over ranges of 2048 samples (FLEX_SPLIT in csrc/ntx_train.hip), the ranges added in ascending order: 21 000 samples
+    """dW = X^T . dY is summed over ranges of 2048 samples (FLEX_SPLIT in csrc/ntx_backend_flex.hip), the ranges added in ascending order: 21 000 samples
     are ten whole ranges and one of 520, 2870 samples one whole range and one of 822.  70 samples a ray also cross the composite's 64-sample chunk."""
     model, spec, wts = make_model((1, 6), dense_media=True, arch=dict(width=64, depth=3))
     assert (n * S) % 2048 not in (0, 1024) and n * S > 2048
