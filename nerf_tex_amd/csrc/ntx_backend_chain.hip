@@ -168,7 +168,7 @@ struct ChainBackend : Backend {
     float *act_at(int i) const { return act + (size_t)i * act_stride; }
     float *gout_at(int i) const { return gout + (size_t)i * gout_stride; }
     unsigned chain_grid(const StepRays &r) const { return (unsigned)std::min<long long>(t->cus, (r.n_blocks() + 3) / 4); }      // persistent: a workgroup of four waves per CU
-    size_t plan_layers(int Kp, int Kd);
+    size_t plan_layers(const ntx_model_desc &d, bool ipe);
     void build_pack();
     void build_dw_jobs();
     int forward(const StepRays &r, hipStream_t st) override;
@@ -176,9 +176,11 @@ struct ChainBackend : Backend {
     int activation(int layer, int64_t n_samples_total, float *out_host) override;
 };
 
-// the forward chain's build for these segment lengths, or the longest one (the streams are then padded with zero rows), and the layers'
+// the forward chain's build for the model's segment lengths, or the longest one (the streams are then padded with zero rows), and the layers'
 // places in the Keras-order blob; returns the blob's floats
-size_t ChainBackend::plan_layers(int Kp, int Kd) {
+size_t ChainBackend::plan_layers(const ntx_model_desc &d, bool ipe) {
+    const ntx::BlobView n = ntx::view_blob(ntx::tuned_arch(1), ntx::dims_of(&d), ipe);
+    const int Kp = n.pos_map, Kd = n.dir_map;
     ptiles = (Kp + 31) / 32; dtiles = (Kd + 31) / 32;
     const int psg = ((Kp + 1) / 2 + 3) / 4, dsg = ((Kd + 1) / 2 + 3) / 4;
     fwd_variant = 3;                                     // the smallest build that holds both segments
@@ -186,12 +188,9 @@ size_t ChainBackend::plan_layers(int Kp, int Kd) {
         if (FWD_VARIANTS[v][0] >= psg && FWD_VARIANTS[v][1] >= dsg &&
             FWD_VARIANTS[v][0] + FWD_VARIANTS[v][1] <= FWD_VARIANTS[fwd_variant][0] + FWD_VARIANTS[fwd_variant][1]) fwd_variant = v;
     PS = 4 * FWD_VARIANTS[fwd_variant][0]; DS = 4 * FWD_VARIANTS[fwd_variant][1];
-    size_t p = 0;
-    auto take = [&](int in, int o) { TLayer l{in, o, p, p + (size_t)in * o}; p += (size_t)in * o + o; return l; };
-    int k = Kp;
-    for (int i = 0; i < 8; ++i) { trunk[i] = take(k, 256); k = 256 + (i == 4 ? Kp : 0); }       // model.py:104-108
-    feature = take(256, 256); c1 = take(256 + Kd, 256); c2 = take(256, 128); rgb = take(128, 3); alpha = take(256, 1);   // Keras order: alpha last
-    return p;
+    std::copy(n.trunk.begin(), n.trunk.end(), trunk);
+    feature = n.feature; c1 = n.colour[0]; c2 = n.c2; rgb = n.rgb; alpha = n.alpha;
+    return n.count;
 }
 
 // the two weight streams and the aux block: what lies where, and what pack_kernel gathers it from
@@ -447,18 +446,18 @@ int chain_check(const ntx_model_desc *desc, TrainDims *dims) {
                                                 "Fourier features on n_pos 3 or IPE on n_pos 6); other architectures train through ntx_trainer_create_flex");
     if (desc->n_geo < 0 || desc->n_app < 0 || desc->n_geo + desc->n_app > 16) return ntx_set_error(NTX_E_INVALID, "n_parameters out of range");
     if (desc->pos_freq < 0 || desc->dir_freq < 0 || desc->param_freq < 0) return ntx_set_error(NTX_E_INVALID, "negative band count");
-    const int Kp = (ipe ? 6 * desc->pos_freq : 3 * (1 + 2 * desc->pos_freq)) + desc->n_geo * (1 + 2 * desc->param_freq), Kd = 3 * (1 + 2 * desc->dir_freq) + desc->n_app * (1 + 2 * desc->param_freq);
+    const int Kp = ntx::pos_map_m(ntx::dims_of(desc), ipe), Kd = ntx::dir_map_m(ntx::dims_of(desc));
     if (Kp > 8 * MAX_PB_GROUPS || Kd > 8 * MAX_PB_GROUPS)
         return ntx_set_error(NTX_E_UNSUPPORTED, "training: pos_map (%d) / dir_map (%d) wider than %d features (the chain holds a block's encoded inputs in registers)", Kp, Kd,
                              8 * MAX_PB_GROUPS);
-    dims->desc = *desc; dims->Kp = Kp; dims->Kd = Kd; dims->ipe = ipe; dims->n_weights = ChainBackend().plan_layers(Kp, Kd);
+    dims->desc = *desc; dims->Kp = Kp; dims->Kd = Kd; dims->ipe = ipe; dims->n_weights = ChainBackend().plan_layers(*desc, ipe);
     return NTX_OK;
 }
 
 int chain_backend_create(ntx_trainer *t) {
     ChainBackend *c = new ChainBackend();
     t->backend = c; c->t = t;
-    c->plan_layers(t->Kp, t->Kd);
+    c->plan_layers(t->desc, t->ipe);
     DeviceMemory &mem = t->mem;
     const long long NB = t->cap_blocks;
     // rows of the encoded inputs beyond Kp / Kd meet zero weights and are never written: they have to be finite

@@ -141,13 +141,6 @@ struct FlexLayer {
 };
 
 inline int pad4(int n) { return (n + 3) & ~3; }
-unsigned flex_skip_mask(const ntx_model_desc *d) {
-    if (d->skip < 0) return 0u;
-    if (d->skip & NTX_SKIP_MASK) return (unsigned)d->skip & (NTX_SKIP_MASK - 1u);
-    return d->skip < 30 ? 1u << d->skip : 0u;
-}
-unsigned flex_trunk_skips(const ntx_model_desc *d) { return flex_skip_mask(d) & ((1u << (d->depth > 1 ? d->depth - 1 : 0)) - 1u); }
-
 struct FlexBackend : Backend {
     ntx_trainer *t = nullptr;
     std::vector<FlexLayer> layers;
@@ -159,37 +152,30 @@ struct FlexBackend : Backend {
     float *wt = nullptr; FlexTSeg *tseg = nullptr; int n_tseg = 0; long long t_total = 0;
     float *partial = nullptr, *colsum = nullptr;        // [n_split][in * out], [n_split][out] of the layer whose weight gradient is being taken
     FlexDst pos_dst[FLEX_MAX_DST]; int n_pos_dst = 0; FlexDst dir_dst{};
-    size_t plan(const ntx_model_desc *d, int Kp, int Kd);
+    size_t plan(const ntx_model_desc *d);
     void place();
     int forward(const StepRays &r, hipStream_t st) override;
     int backward(const StepRays &r, hipStream_t st) override;
     int activation(int layer, int64_t n_samples_total, float *out_host) override;
 };
 
-// the layers of the architecture in forward order with their places in the Keras-order blob (model.layer_table(): trunk, feature, colour
-// hidden layers, colour half, color, alpha); returns the blob's floats
-size_t FlexBackend::plan(const ntx_model_desc *d, int Kp, int Kd) {
-    const int depth = d->depth, w = d->width, cd = d->kind == NTX_MODEL_NERF ? 0 : d->color_depth;
-    const unsigned skips = flex_trunk_skips(d);
-    size_t p = 0;
-    auto add = [&](int in, int out, int enc, int src, int relu) {
-        FlexLayer l; l.in = in; l.out = out; l.enc = enc; l.src = src; l.relu = relu; l.w = p; l.b = p + (size_t)in * out;
-        p += (size_t)in * out + out;
+// the layers of the architecture in forward order with their places in the Keras-order blob (ntx_arch.h: view_blob); returns the blob's floats
+size_t FlexBackend::plan(const ntx_model_desc *d) {
+    const ntx::BlobView n = ntx::view_blob(ntx::trunk_arch_of(d), ntx::dims_of(d));      // (base fields only: the handle keeps no extended descriptor, and branches are refused)
+    const int depth = (int)n.trunk.size(), cd = (int)n.colour.size();
+    auto add = [&](const TLayer &t, int enc, int src, int relu) {
+        FlexLayer l; l.in = t.in; l.out = t.out; l.enc = enc; l.src = src; l.relu = relu; l.w = t.w; l.b = t.b;
         layers.push_back(l);
         if (relu) relu_layers.push_back((int)layers.size() - 1);
     };
-    for (int i = 0; i < depth; ++i) {
-        const int enc = i == 0 ? Kp : (((skips >> (i - 1)) & 1u) ? Kp : 0);
-        add(i == 0 ? Kp : w + enc, w, enc, i - 1, 1);
-    }
+    for (int i = 0; i < depth; ++i) add(n.trunk[i], i == 0 ? n.pos_map : n.trunk[i].in - d->width, i - 1, 1);   // enc: pos_map, also where a skip concatenates it (model.py:107-108)
     last_trunk = depth - 1;
-    add(w, w, 0, depth - 1, 0);                                              // the feature layer: no activation (model.py:114)
-    for (int i = 0; i < cd; ++i) add(i == 0 ? w + Kd : w, w, i == 0 ? Kd : 0, depth + i, 1);
-    add(cd > 0 ? w : w + Kd, w / 2, cd > 0 ? 0 : Kd, depth + cd, 1);         // :122
+    add(n.feature, 0, depth - 1, 0);                                         // the feature layer: no activation (model.py:114)
+    for (int i = 0; i < cd; ++i) add(n.colour[i], i == 0 ? n.dir_map : 0, depth + i, 1);
+    add(n.c2, cd > 0 ? 0 : n.dir_map, depth + cd, 1);                        // :122
     half = (int)layers.size() - 1;
-    rgb = TLayer{w / 2, 3, p, p + (size_t)(w / 2) * 3}; p += (size_t)(w / 2) * 3 + 3;
-    alpha = TLayer{w, 1, p, p + (size_t)w}; p += (size_t)w + 1;
-    return p;
+    rgb = n.rgb; alpha = n.alpha;
+    return n.count;
 }
 
 // a buffer per layer, [the encoding of the concatenation behind it | its output], rows padded to 16 bytes; the first layer reads pos_map.
@@ -199,7 +185,7 @@ void FlexBackend::place() {
     const ntx_model_desc &d = t->desc;
     const long long M = t->cap;
     const int Kp = t->Kp, Kd = t->Kd;
-    const unsigned skips = flex_trunk_skips(&d);
+    const unsigned skips = ntx::trunk_skips(&d);
     float *pos = nullptr;
     mem.alloc(&pos, (size_t)M * pad4(Kp));
     pos_dst[n_pos_dst++] = FlexDst{pos, pad4(Kp)};
@@ -320,7 +306,7 @@ int FlexBackend::activation(int layer, int64_t n_samples_total, float *out_host)
 }
 }   // namespace
 namespace ntx_train {
-// the architectures the flex render family takes (nerftex.hip: find_variant) without parameter branches
+// the architectures the flex render family takes (ntx_arch.h: find_variant) without parameter branches
 int flex_check(const ntx_model_desc *desc, TrainDims *dims) {
     const bool nerf = desc->kind == NTX_MODEL_NERF;
     if (desc->kind != NTX_MODEL_PARAMNERF && desc->kind != NTX_MODEL_NERF && desc->kind != NTX_MODEL_PARAMNERF_EX) return ntx_set_error(NTX_E_UNSUPPORTED, "training: model kind %d", desc->kind);
@@ -332,7 +318,7 @@ int flex_check(const ntx_model_desc *desc, TrainDims *dims) {
     if (desc->depth < 1 || desc->depth > FLEX_MAX_DEPTH || desc->width < 2 || desc->width > 256 || cd < 0 || cd > FLEX_MAX_COLOR)
         return ntx_set_error(NTX_E_UNSUPPORTED, "training: depth %d width %d color_depth %d (built: depth 1..%d, width 2..256, color_depth 0..%d)", desc->depth, desc->width, cd,
                              FLEX_MAX_DEPTH, FLEX_MAX_COLOR);
-    if ((desc->skip >= 0 && !(desc->skip & NTX_SKIP_MASK) && desc->skip >= 30) || ((flex_skip_mask(desc) >> (desc->depth - 1)) & 1u))
+    if ((desc->skip >= 0 && !(desc->skip & NTX_SKIP_MASK) && desc->skip >= 30) || ((ntx::skip_mask_of(desc) >> (desc->depth - 1)) & 1u))
         return ntx_set_error(NTX_E_UNSUPPORTED, "training: a skip behind the last trunk layer (it widens the density head and the feature layer, model.py:107-114) is not built");
     if (n_geo < 0 || n_geo > 4 || n_app < 0 || n_app > 8 || desc->pos_freq < 0 || desc->pos_freq > 10 || desc->dir_freq < 0 || desc->dir_freq > 4 ||
         (n_geo + n_app > 0 && (desc->param_freq < 0 || desc->param_freq > 4)))
@@ -340,15 +326,15 @@ int flex_check(const ntx_model_desc *desc, TrainDims *dims) {
                              desc->dir_freq, desc->param_freq);
     const int pfq = n_geo + n_app > 0 ? desc->param_freq : 0;
     dims->desc = *desc; dims->desc.n_geo = n_geo; dims->desc.n_app = n_app; dims->desc.param_freq = pfq; dims->ipe = false;
-    dims->Kp = 3 * (1 + 2 * desc->pos_freq) + n_geo * (1 + 2 * pfq); dims->Kd = 3 * (1 + 2 * desc->dir_freq) + n_app * (1 + 2 * pfq);
-    dims->n_weights = FlexBackend().plan(desc, dims->Kp, dims->Kd);
+    dims->Kp = ntx::pos_map_m(ntx::dims_of(desc), 0); dims->Kd = ntx::dir_map_m(ntx::dims_of(desc));
+    dims->n_weights = FlexBackend().plan(desc);
     return NTX_OK;
 }
 
 int flex_backend_create(ntx_trainer *t) {
     FlexBackend *f = new FlexBackend();
     t->backend = f; f->t = t;
-    f->plan(&t->desc, t->Kp, t->Kd);
+    f->plan(&t->desc);
     f->place();
     return t->mem.rc;
 }

@@ -1,5 +1,6 @@
 // ntx_small_kernels.h -- the bandwidth-bound stand-alone kernels (composite, ray generation, Fourier
-// features).  Included by nerftex.hip only; the MFMA kernels are in ntx_device.h / ntx_variant.hip.
+// features) and the small kernels of the context's entries.  Included by ntx_standalone.hip only, which launches every one of them; the
+// MFMA kernels are in ntx_device.h / ntx_variant.hip.
 #pragma once
 
 #include "ntx_device.h"
@@ -464,6 +465,23 @@ __global__ __launch_bounds__(256) void sample_depths_kernel(const float *t, int6
     const float t0 = t[2 * ray], t1 = t[2 * ray + 1];
     z_out[k] = (flags & NTX_FLAG_PERTURB) ? z_jittered(delta, global_index(idx0, idx_run, idx_stride, ray), i, t0, t1, npts, seed_lo, seed_hi)
                                           : z_lin(delta, i, t0, t1, npts);
+}
+
+// packed[i] = idx[i] >= 0 ? w[idx[i]] : konst[i]: the weight image remade where the weights are
+__global__ void gather_weights_kernel(const float *__restrict__ w, const int32_t *__restrict__ idx, const float *__restrict__ konst, size_t n, float *__restrict__ packed) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t g = idx[i];
+    packed[i] = g >= 0 ? w[g] : konst[i];
+}
+
+// noise_out[ray][i] = raw_noise_std * N(0,1): the very draws the render kernels add to the density (ntx_device.h normal01)
+__global__ __launch_bounds__(256) void sample_noise_kernel(int64_t n_rays, int npts, float noise_std, uint32_t seed_lo, uint32_t seed_hi, int64_t idx0,
+                                                           uint32_t idx_run, int64_t idx_stride, float *noise_out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_rays * npts) return;
+    const int64_t ray = k / npts;
+    noise_out[k] = noise_std * normal01(global_index(idx0, idx_run, idx_stride, ray), (int)(k % npts), seed_lo, seed_hi);
 }
 
 }  // namespace ntx

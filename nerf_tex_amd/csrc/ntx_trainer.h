@@ -3,12 +3,11 @@
 // layer by layer), the owner of its device memory, and the launchers of the kernels more than one unit uses (no relocatable device code: a
 // kernel is launched by a host function of the unit that defines it).
 #pragma once
-#include "nerftex.h"
+#include "ntx_arch.h"   // the model's dimensions and the one view of its blob; ntx_set_error
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <vector>
 
-extern "C" int ntx_set_error(int code, const char *fmt, ...);   // nerftex.hip
 #define TRAIN_TRY(expr)                                                                                  \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
@@ -54,7 +53,7 @@ struct Backend {
 };
 // what an entry's architecture check makes of a descriptor
 struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; };
-struct TLayer { int in, out; size_t w, b; };      // offsets into the Keras-order blob (kernel [in][out], then bias)
+using TLayer = ntx::BlobLayer;                    // offsets into the Keras-order blob (kernel [in][out], then bias)
 }   // namespace ntx_train
 
 struct ntx_trainer {

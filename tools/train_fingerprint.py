@@ -67,10 +67,15 @@ def ipe(blur_idx):
     return fingerprint(tr, (ro, rd, t, params, cone, *targets(n, 2)), make_loss("alpha_smape")[1])
 
 
-def flex(arch_id, n=45, S=37, **kw):
+def flex(arch_id, n=45, S=37, extended=False, **kw):
+    """`extended`: the same model through an ntx_model_desc_ex with param_depth 0 (kind NTX_MODEL_PARAMNERF_EX), which the C ABI takes: same bits"""
+    from nerf_tex_amd import _lib
     from nerf_tex_amd.train import FlexTrainer
     _, npar, kind, arch, fam = next(a for a in ARCHS if a[0] == arch_id)
     model, _, _ = make_model(npar, kind=kind, arch=arch, dense_media=True)
+    if extended:
+        plain = model.desc
+        model.desc = lambda: _lib.ModelDesc(_lib.KIND_PARAMNERF_EX, *[getattr(plain(), f) for f, _ in _lib.ModelDesc._fields_[1:12]], 0, 128)
     tr = FlexTrainer(model, max_rays=n, n_samples=S, perturb=True, **kw)
     return fingerprint(tr, family_batch(fam, n, S, sum(npar)), make_loss("alpha_smape")[1])
 
@@ -115,6 +120,7 @@ CASES = [
     ("flex color_depth2", lambda: flex("color_depth2")),
     ("flex depth1", lambda: flex("depth1")),
     ("flex w128_d4 grass_filtered 41x70 blur0", lambda: flex("w128_d4", 41, 70, blur_idx=0)),                            # 2870 samples: two ranges of the 2048-sample split
+    ("flex w128_d4 grass_filtered 41x70 blur0, extended descriptor", lambda: flex("w128_d4", 41, 70, blur_idx=0, extended=True)),  # the line above again
     ("flex coarse + fine Nerfs 16x(16+16)", coarse_fine),                                                                 # ntx_trainer_composite_weights
     ("gemm 300x200x77 A k-contiguous", lambda: gemm(1, 300, 200, 77)),
     ("gemm 337x256x1000 A transposed", lambda: gemm(0, 337, 256, 1000)),
@@ -122,9 +128,13 @@ CASES = [
 
 
 def main():
+    lines = {}
     for name, run in CASES:
         try:
-            print(json.dumps({"case": name, **run()}), flush=True)
+            lines[name] = run()
+            print(json.dumps({"case": name, **lines[name]}), flush=True)
+            if name.endswith(", extended descriptor") and lines[name] != lines[name[:-len(", extended descriptor")]]:
+                raise ValueError("an extended descriptor with param_depth 0 trains to other bits than the plain one")
         except Exception:                                   # (nothing more is started on a device that may just have faulted)
             print(json.dumps({"case": name, "error": traceback.format_exc(limit=3)}), flush=True)
             return 1
