@@ -590,6 +590,23 @@ int ntx_gemm_f32(const float *A, int lda, int a_kcontig, const float *B, int ldb
  * 65 = the raw colour [n_samples_total][3]. */
 int ntx_trainer_create_flex(const ntx_model_desc *desc, const float *weights_host, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray,
                             ntx_trainer **out);
+/* The same trainer for a ParamNerf WITH parameter branches (ABI v7, appended): desc->base.kind must be NTX_MODEL_PARAMNERF_EX; everything
+ * ntx_trainer_create_flex takes for a ParamNerf, plus param_depth 0..4 and param_width 2..128 (the render side's limits).  A branch exists
+ * only where its parameter count is > 0 (model.py:88, 96).  NTX_E_UNSUPPORTED, before any device is asked for: an IPE model, a skip at
+ * depth - 1, width > 256, param_depth outside 0..4, param_width outside 2..128 when param_depth > 0; then NTX_E_INVALID as above.
+ * ntx_trainer_create and ntx_trainer_create_flex keep refusing param_depth > 0.  The handle is an ordinary ntx_trainer; weights, gradients
+ * and Adam's moments are in Keras get_weights() order, branch layers included (the geometry branch before the trunk, the appearance branch
+ * among the trunk layers of its graph depth).  With param_depth = 0 the step is bit for bit ntx_trainer_create_flex's.
+ * The step: the Fourier features of a branch's parameters go to that branch's own input rows, per sample (blur_idx on a geometry parameter
+ * makes them differ from sample to sample); each branch layer is one contraction with ReLU, every output kept; the last output is copied
+ * behind FF(pos) / FF(dir) into every buffer that starts with pos_map / dir_map.  On the way back every reader of a branch's output (trunk
+ * layer 0 and the layers behind a skip; the first colour layer, or the colour half layer when color_depth = 0) adds dY . W[branch rows]^T
+ * into the branch's gradient in descending layer order, masked by the branch's last ReLU, and the branch's layers follow like the trunk's.
+ * A step stays bit-reproducible and independent of the trainer's capacity.
+ * ntx_trainer_activation on such a handle: as ntx_trainer_create_flex's, and 32 + j = the kept output of geometry branch layer j, 48 + j =
+ * that of appearance branch layer j, each [n_samples_total][param_width]; NTX_E_INVALID for a branch the model does not have. */
+int ntx_trainer_create_flex_ex(const ntx_model_desc_ex *desc, const float *weights_host, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray,
+                               ntx_trainer **out);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,7 @@ SYMBOLS = {
     "ntx_gemm_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "ntx_instancer_model_input": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_uint64, _op] + [_vp] * 12),
     "ntx_trainer_create_flex": (C.c_int, [C.POINTER(ModelDesc), _fp, C.c_size_t, C.c_int, C.c_int64, C.c_int, C.POINTER(_vp)]),
+    "ntx_trainer_create_flex_ex": (C.c_int, [C.POINTER(ModelDesc), _fp, C.c_size_t, C.c_int, C.c_int64, C.c_int, C.POINTER(_vp)]),
 }
 
 

@@ -1,6 +1,8 @@
-// ntx_backend_flex.hip -- the layer-by-layer backend of a training step (ntx_trainer_create_flex): any Nerf / ParamNerf the flex render
-// family takes (other depths, widths, skips, color_depth) on row-major activations -- flex_encode_kernel, one contraction (ntx_gemm.hip) per
-// Dense layer and pass, the narrow heads on flex_head_*_kernel.  The handle, the composite, the loss and Adam are ntx_trainer.hip's.  gfx950 only.
+// ntx_backend_flex.hip -- the layer-by-layer backend of a training step (ntx_trainer_create_flex, ntx_trainer_create_flex_ex): any Nerf /
+// ParamNerf the flex render family takes (other depths, widths, skips, color_depth; through the _ex entry also param_depth > 0) on row-major
+// activations -- flex_encode_kernel, one contraction (ntx_gemm.hip) per Dense layer and pass, the narrow heads on flex_head_*_kernel, a
+// parameter branch's output into the concatenations by flex_branch_copy_kernel.  The handle, the composite, the loss and Adam are
+// ntx_trainer.hip's.  gfx950 only.
 #include <algorithm>
 #include "ntx_trainer.h"
 #include "ntx_encode.h"
@@ -14,8 +16,9 @@ constexpr int FLEX_MAX_DEPTH = 24, FLEX_MAX_COLOR = 4, FLEX_MAX_DST = FLEX_MAX_D
 constexpr int FLEX_SPLIT = 2048;                       // samples per partial sum of a weight gradient: a function of nothing, so a step's sums do not depend on the trainer's capacity
 struct FlexDst { float *p; int ld; };                  // where a map goes: row m starts at p + m * ld
 struct FlexEncodeArgs {
-    StepRays r; int Kp, Kd;
+    StepRays r; int Kp, Kd;                            // features the encoder writes per map: FF(xyz) and FF(that map's parameters)
     FlexDst pos[FLEX_MAX_DST], dir; int n_pos_dst;
+    FlexDst geo_in, app_in;                            // p != NULL: a parameter branch (model.py:88-101) takes that map's parameter features as its input rows
     float *dists;
 };
 // ntx_encode.h's values as rows [sample][feature]: thread per sample and feature, blockIdx.y = the map
@@ -36,11 +39,25 @@ __global__ __launch_bounds__(256) void flex_encode_kernel(FlexEncodeArgs args) {
         if (!xyz) return blurred_param(rc.pr, part == 0 ? c : a.n_geo + c, a.blur_idx, hit, a.cone, ray, z);     // model.py:88-93, 96-101
         return part == 0 ? rc.point(a.rays_o[3 * ray + c], c, z) : rc.dir(c);
     });
-    if (part == 0) for (int i = 0; i < args.n_pos_dst; ++i) args.pos[i].p[(size_t)m * args.pos[i].ld + f] = v;
+    const FlexDst &branch = part == 0 ? args.geo_in : args.app_in;
+    if (!xyz && branch.p) branch.p[(size_t)m * branch.ld + (f - K3)] = v;                      // the branch's output goes behind FF(xyz) instead: flex_branch_copy_kernel
+    else if (part == 0) for (int i = 0; i < args.n_pos_dst; ++i) args.pos[i].p[(size_t)m * args.pos[i].ld + f] = v;
     else {
         args.dir.p[(size_t)m * args.dir.ld + f] = v;
         if (f == 0) args.dists[(size_t)ray * a.S + s] = sample_dist(zray, s, a.S, z, hit, rc.dn);
     }
+}
+
+// The output of a parameter branch's last layer, src[m][c] for c < width, behind the FF(xyz) columns of every buffer that starts with the map
+// (model.py:93, 101): dst[i].p[m][off + c].  Read once, written n_dst times; thread per element, consecutive threads along the row.  off is
+// 63 / 27 at the configs' bands, so the destinations are not 16-byte aligned: dwords
+struct FlexBranchCopyArgs { const float *src; int lds, width, off, n_dst; FlexDst dst[FLEX_MAX_DST]; long long M; };
+__global__ __launch_bounds__(256) void flex_branch_copy_kernel(FlexBranchCopyArgs a) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.M * a.width) return;
+    const long long m = e / a.width; const int c = (int)(e - m * a.width);
+    const float v = a.src[(size_t)m * a.lds + c];
+    for (int i = 0; i < a.n_dst; ++i) a.dst[i].p[(size_t)m * a.dst[i].ld + a.off + c] = v;
 }
 
 // A narrow head (density: 1 column, colour: 3): out[m][c] = b[c] + sum_k X[m][k] W[k][c], K <= 256.  A wave per row, the row's sum
@@ -138,6 +155,16 @@ struct FlexLayer {
     const float *X = nullptr; int ldx = 0;
     float *Y = nullptr; int ldy = 0;
     long long wt = -1;                                  // its transposed hidden rows [out][in - enc] in FlexBackend::wt
+    long long bwt = -1;                                 // a consumer of a parameter branch: its transposed branch rows [out][param_width] in FlexBackend::wt
+};
+// A parameter branch (model.py:88-93 geometry, 96-101 appearance): param_depth Dense(param_width, relu) layers on FF(parameters), per sample
+// (with blur_idx on one of its parameters the input differs from sample to sample).  Layer j's X is the input buffer / layer j - 1's Y; every Y
+// is a buffer of its own [M][pad4(param_width)]: the ReLU mask on the way back.  Its consumers read copies of the last Y in their own rows.
+struct FlexBranch {
+    std::vector<FlexLayer> layers;
+    float *in = nullptr; int ld_in = 0, n_in = 0, off = 0;      // the input rows [M][ld_in], n_in features; off: the columns of FF(xyz) in front of it in a map
+    int consumers_met = 0;                                      // of the current way back
+    bool exists() const { return !layers.empty(); }
 };
 
 inline int pad4(int n) { return (n + 3) & ~3; }
@@ -147,22 +174,40 @@ struct FlexBackend : Backend {
     std::vector<int> relu_layers;                       // the oracle's mask order: trunk, colour hidden layers, colour half
     TLayer rgb{}, alpha{};
     int last_trunk = 0, half = 0;                       // indices into layers
+    FlexBranch geo, app; int pw = 0, ldb = 0;           // the parameter branches, param_width and the rows of their buffers
+    int Kp = 0, Kd = 0, enc_Kp = 0, enc_Kd = 0;         // features of pos_map / dir_map as the layers see them; as the encoder writes them (the same without branches)
     int ldg = 0;
     float *G[2] = {nullptr, nullptr};                   // the gradient at a layer's output, ping-pong
+    float *BG[2] = {nullptr, nullptr};                  // ... at a branch layer's output [M][ldb] (param_width may be larger than width)
     float *wt = nullptr; FlexTSeg *tseg = nullptr; int n_tseg = 0; long long t_total = 0;
     float *partial = nullptr, *colsum = nullptr;        // [n_split][in * out], [n_split][out] of the layer whose weight gradient is being taken
     FlexDst pos_dst[FLEX_MAX_DST]; int n_pos_dst = 0; FlexDst dir_dst{};
-    size_t plan(const ntx_model_desc *d);
+    size_t plan(const ntx_model_desc *d, int param_depth, int param_width);
     void place();
+    void branch_forward(const FlexBranch &b, const FlexDst *dst, int n_dst, long long M, hipStream_t st);
+    void branch_term(FlexBranch &b, const FlexLayer &consumer, const float *dY, long long M, hipStream_t st);
+    void branch_backward(const FlexBranch &b, long long M, int n_split, hipStream_t st);
+    void reduce(hipStream_t st, int n_split, const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out);
     int forward(const StepRays &r, hipStream_t st) override;
     int backward(const StepRays &r, hipStream_t st) override;
     int activation(int layer, int64_t n_samples_total, float *out_host) override;
 };
 
 // the layers of the architecture in forward order with their places in the Keras-order blob (ntx_arch.h: view_blob); returns the blob's floats
-size_t FlexBackend::plan(const ntx_model_desc *d) {
-    const ntx::BlobView n = ntx::view_blob(ntx::trunk_arch_of(d), ntx::dims_of(d));      // (base fields only: the handle keeps no extended descriptor, and branches are refused)
+size_t FlexBackend::plan(const ntx_model_desc *d, int param_depth, int param_width) {
+    ntx_model_desc_ex x{};                                                   // (the handle keeps the base struct and the two fields behind it: put together again for flex_arch_of)
+    x.base = *d; x.param_depth = param_depth; x.param_width = param_width;
+    if (param_depth > 0) x.base.kind = NTX_MODEL_PARAMNERF_EX;
+    const ntx::Dims dm = ntx::dims_of(d);
+    const ntx::BlobView n = ntx::view_blob(param_depth > 0 ? ntx::flex_arch_of(&x.base) : ntx::trunk_arch_of(d), dm);
     const int depth = (int)n.trunk.size(), cd = (int)n.colour.size();
+    Kp = n.pos_map; Kd = n.dir_map; enc_Kp = ntx::pos_map_m(dm, 0); enc_Kd = ntx::dir_map_m(dm);
+    pw = param_depth > 0 ? param_width : 0;
+    auto branch = [&](FlexBranch &b, const std::vector<TLayer> &ls, int n_act, int off) {
+        for (const TLayer &t : ls) { FlexLayer l; l.in = t.in; l.out = t.out; l.relu = 1; l.w = t.w; l.b = t.b; b.layers.push_back(l); }
+        b.n_in = ntx::par_emb_m(n_act, dm); b.off = off;
+    };
+    branch(geo, n.pgeo, dm.g, ntx::pos_emb_m(dm, 0)); branch(app, n.papp, dm.a, ntx::dir_emb_m(dm));
     auto add = [&](const TLayer &t, int enc, int src, int relu) {
         FlexLayer l; l.in = t.in; l.out = t.out; l.enc = enc; l.src = src; l.relu = relu; l.w = t.w; l.b = t.b;
         layers.push_back(l);
@@ -179,12 +224,11 @@ size_t FlexBackend::plan(const ntx_model_desc *d) {
 }
 
 // a buffer per layer, [the encoding of the concatenation behind it | its output], rows padded to 16 bytes; the first layer reads pos_map.
-// Then the gradients' ping-pong, the weight gradients' partial sums and the transposed kernels with their table
+// Then the branches' buffers, the gradients' ping-pongs, the weight gradients' partial sums and the transposed kernels with their table
 void FlexBackend::place() {
     DeviceMemory &mem = t->mem;
     const ntx_model_desc &d = t->desc;
     const long long M = t->cap;
-    const int Kp = t->Kp, Kd = t->Kd;
     const unsigned skips = ntx::trunk_skips(&d);
     float *pos = nullptr;
     mem.alloc(&pos, (size_t)M * pad4(Kp));
@@ -205,6 +249,19 @@ void FlexBackend::place() {
     }
     ldg = pad4(d.width);
     mem.alloc(&G[0], (size_t)M * ldg); mem.alloc(&G[1], (size_t)M * ldg);
+    ldb = pad4(pw);
+    for (FlexBranch *b : {&geo, &app}) {
+        if (!b->exists()) continue;
+        b->ld_in = pad4(b->n_in);
+        mem.alloc(&b->in, (size_t)M * b->ld_in);
+        for (size_t j = 0; j < b->layers.size(); ++j) {
+            FlexLayer &l = b->layers[j];
+            l.ldy = ldb; mem.alloc(&l.Y, (size_t)M * ldb);
+            if (j == 0) { l.X = b->in; l.ldx = b->ld_in; } else { l.X = b->layers[j - 1].Y; l.ldx = ldb; }
+            most_dw = std::max(most_dw, (size_t)l.in * l.out);
+        }
+    }
+    if (geo.exists() || app.exists()) { mem.alloc(&BG[0], (size_t)M * ldb); mem.alloc(&BG[1], (size_t)M * ldb); }
     const size_t splits = (size_t)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
     mem.alloc(&partial, splits * most_dw); mem.alloc(&colsum, splits * 256);
     std::vector<FlexTSeg> segs;
@@ -216,9 +273,37 @@ void FlexBackend::place() {
         segs.push_back(FlexTSeg{(long long)(l.w + (size_t)l.enc * l.out), at, at, (long long)hid * l.out, hid, l.out});
         at += ((long long)hid * l.out + 3) / 4 * 4;
     }
+    // ... and the branch rows of the kernels that read a branch's output (behind the FF(xyz) rows of the map), the kernels of the branches'
+    // own hidden layers whole
+    auto seg = [&](long long &slot, size_t src, int rows, int out) {
+        slot = at;
+        segs.push_back(FlexTSeg{(long long)src, at, at, (long long)rows * out, rows, out});
+        at += ((long long)rows * out + 3) / 4 * 4;
+    };
+    for (size_t i = 0; i < layers.size(); ++i) {
+        FlexLayer &l = layers[i];
+        const bool pos_in = (int)i < d.depth && l.enc > 0, dir_in = (int)i == d.depth + 1;     // layers that read pos_map / dir_map
+        if (pos_in && geo.exists()) seg(l.bwt, l.w + (size_t)geo.off * l.out, pw, l.out);
+        if (dir_in && app.exists()) seg(l.bwt, l.w + (size_t)app.off * l.out, pw, l.out);
+    }
+    for (FlexBranch *b : {&geo, &app})
+        for (size_t j = 1; j < b->layers.size(); ++j) seg(b->layers[j].wt, b->layers[j].w, b->layers[j].in, b->layers[j].out);
     t_total = at; n_tseg = (int)segs.size();
     mem.alloc(&wt, (size_t)at);
     mem.upload(&tseg, segs, "segment");
+}
+
+// a branch's layers, then its last output into the concatenations that hold the map
+void FlexBackend::branch_forward(const FlexBranch &b, const FlexDst *dst, int n_dst, long long M, hipStream_t st) {
+    const float *W = t->w;
+    for (const FlexLayer &l : b.layers) {
+        GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = W + l.w; g.ldb = l.out; g.C = l.Y; g.ldc = l.ldy; g.M = (int)M; g.N = l.out; g.K = l.in; g.bias = W + l.b; g.relu = 1;
+        launch_gemm(st, true, g);
+    }
+    const FlexLayer &last = b.layers.back();
+    FlexBranchCopyArgs c{}; c.src = last.Y; c.lds = last.ldy; c.width = pw; c.off = b.off; c.n_dst = n_dst; c.M = M;
+    for (int i = 0; i < n_dst; ++i) c.dst[i] = dst[i];
+    hipLaunchKernelGGL(flex_branch_copy_kernel, dim3((unsigned)((M * pw + 255) / 256)), dim3(256), 0, st, c);
 }
 
 int FlexBackend::forward(const StepRays &r, hipStream_t st) {
@@ -226,12 +311,17 @@ int FlexBackend::forward(const StepRays &r, hipStream_t st) {
     const float *W = t->w;
     hipLaunchKernelGGL(flex_transpose_kernel, dim3((unsigned)((t_total + 255) / 256)), dim3(256), 0, st, W, wt, tseg, n_tseg, t_total);
     {
-        FlexEncodeArgs e{}; e.r = r; e.Kp = t->Kp; e.Kd = t->Kd; e.n_pos_dst = n_pos_dst; e.dir = dir_dst; e.dists = t->dists;
+        FlexEncodeArgs e{}; e.r = r; e.Kp = enc_Kp; e.Kd = enc_Kd; e.n_pos_dst = n_pos_dst; e.dir = dir_dst; e.dists = t->dists;
         for (int i = 0; i < n_pos_dst; ++i) e.pos[i] = pos_dst[i];
-        const long long most = M * std::max(t->Kp, t->Kd);
+        if (geo.exists()) e.geo_in = FlexDst{geo.in, geo.ld_in};
+        if (app.exists()) e.app_in = FlexDst{app.in, app.ld_in};
+        const long long most = M * std::max(enc_Kp, enc_Kd);
         hipLaunchKernelGGL(flex_encode_kernel, dim3((unsigned)((most + 255) / 256), 2), dim3(256), 0, st, e);
     }
-    for (const FlexLayer &l : layers) {                                      // a contraction per layer, every output kept
+    if (geo.exists()) branch_forward(geo, pos_dst, n_pos_dst, M, st);        // model.py:88-93: in front of trunk layer 0
+    for (size_t i = 0; i < layers.size(); ++i) {                             // a contraction per layer, every output kept
+        const FlexLayer &l = layers[i];
+        if ((int)i == t->desc.depth + 1 && app.exists()) branch_forward(app, &dir_dst, 1, M, st);      // :96-101: in front of the first layer that reads dir_map
         GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = W + l.w; g.ldb = l.out; g.C = l.Y; g.ldc = l.ldy; g.M = (int)M; g.N = l.out; g.K = l.in; g.bias = W + l.b; g.relu = l.relu;
         launch_gemm(st, true, g);
     }
@@ -244,17 +334,49 @@ int FlexBackend::forward(const StepRays &r, hipStream_t st) {
 
 // the way back from the composite's adjoint dgrad [M][4]: per layer, last to first, dW = X^T . dY over ranges of FLEX_SPLIT samples added in
 // ascending order, then dX = (dY . W[hidden rows]^T) where the stored activation in front is > 0
+void FlexBackend::reduce(hipStream_t st, int n_split, const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
+    ReduceBatch rb{};
+    rb.job[0] = ReduceJob{part, n_split, count, count, 0, t->grad + out, 0};
+    rb.n = 1;
+    if (bias_partial) { rb.job[1] = ReduceJob{bias_partial, n_split, bias_count, bias_count, 0, t->grad + bias_out, (count + 255) / 256 * 256}; rb.n = 2; }
+    launch_reduce(st, rb);
+}
+// A consumer's term of the gradient at a branch's output: BG[0] (+)= dY . W_consumer[branch rows]^T, kept where the branch's last ReLU was
+// open.  The contraction masks after it accumulates, and what it masks is the same in every term, so masking each equals masking the sum.
+void FlexBackend::branch_term(FlexBranch &b, const FlexLayer &consumer, const float *dY, long long M, hipStream_t st) {
+    const FlexLayer &last = b.layers.back();
+    GemmArgs g{}; g.A = dY; g.lda = ldg; g.B = wt + consumer.bwt; g.ldb = pw; g.C = BG[0]; g.ldc = ldb; g.M = (int)M; g.N = pw; g.K = consumer.out;
+    g.accumulate = b.consumers_met++ > 0; g.mask = last.Y; g.ldmask = last.ldy;
+    launch_gemm(st, true, g);
+}
+// ... and from there through the branch, as through the trunk: dW / db per layer over ranges of FLEX_SPLIT samples, dX masked by the layer in
+// front; nothing behind the first layer (the inputs are not trained)
+void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split, hipStream_t st) {
+    int cur = 0;
+    for (int j = (int)b.layers.size() - 1; j >= 0; --j) {
+        const FlexLayer &l = b.layers[j];
+        const float *dY = BG[cur];
+        GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldb; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
+        g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
+        launch_gemm(st, false, g, n_split);
+        reduce(st, n_split, partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
+        if (j == 0) break;
+        const FlexLayer &s = b.layers[j - 1];
+        GemmArgs x{}; x.A = dY; x.lda = ldb; x.B = wt + l.wt; x.ldb = l.in; x.C = BG[cur ^ 1]; x.ldc = ldb; x.M = (int)M; x.N = l.in; x.K = l.out;
+        x.mask = s.Y; x.ldmask = s.ldy;
+        launch_gemm(st, true, x);
+        cur ^= 1;
+    }
+}
+
 int FlexBackend::backward(const StepRays &r, hipStream_t st) {
     const long long M = r.M();
     const float *W = t->w;
     const int n_split = (int)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
     auto reduce = [&](const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
-        ReduceBatch rb{};
-        rb.job[0] = ReduceJob{part, n_split, count, count, 0, t->grad + out, 0};
-        rb.n = 1;
-        if (bias_partial) { rb.job[1] = ReduceJob{bias_partial, n_split, bias_count, bias_count, 0, t->grad + bias_out, (count + 255) / 256 * 256}; rb.n = 2; }
-        launch_reduce(st, rb);
+        this->reduce(st, n_split, part, count, out, bias_partial, bias_count, bias_out);
     };
+    geo.consumers_met = app.consumers_met = 0;
     const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
     const unsigned ew = 256;
     // the colour head (model.py:123): kernel and bias lie side by side in the blob, as in a range's partial sums
@@ -271,6 +393,12 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
             g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
             launch_gemm(st, false, g, n_split);
             reduce(partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
+        }
+        if (l.bwt >= 0) {                                                    // a reader of a branch's output: its term, in the order this loop meets the readers
+            const bool trunk = i <= last_trunk;
+            FlexBranch &b = trunk ? geo : app;
+            branch_term(b, l, dY, M, st);
+            if (!trunk || i == 0) branch_backward(b, M, n_split, st);        // the appearance branch has one reader; trunk layer 0 is the geometry branch's last
         }
         if (i == 0) break;                                                   // the inputs are not trained
         const FlexLayer &s = layers[l.src];
@@ -295,10 +423,12 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
 int FlexBackend::activation(int layer, int64_t n_samples_total, float *out_host) {              // row-major buffers: a strided copy
     const float *from = nullptr; int width = 0, ld = 0;
     if (layer >= 0 && layer < (int)relu_layers.size()) { const FlexLayer &l = layers[relu_layers[layer]]; from = l.Y; width = l.out; ld = l.ldy; }
+    else if (layer >= 32 && layer < 32 + (int)geo.layers.size()) { const FlexLayer &l = geo.layers[layer - 32]; from = l.Y; width = l.out; ld = l.ldy; }
+    else if (layer >= 48 && layer < 48 + (int)app.layers.size()) { const FlexLayer &l = app.layers[layer - 48]; from = l.Y; width = l.out; ld = l.ldy; }
     else if (layer == 64) { from = t->sigma; width = ld = 1; }
     else if (layer == 65) { from = t->raw_rgb; width = ld = 3; }
-    else return ntx_set_error(NTX_E_INVALID, "layer %d (0 .. %d: the ReLU layers in the order trunk, colour layers, colour half; 64 the raw density, 65 the raw colour)", layer,
-                              (int)relu_layers.size() - 1);
+    else return ntx_set_error(NTX_E_INVALID, "layer %d (0 .. %d: the ReLU layers in the order trunk, colour layers, colour half; 32 + j / 48 + j: layer j of the geometry / "
+                              "appearance branch, where the model has it; 64 the raw density, 65 the raw colour)", layer, (int)relu_layers.size() - 1);
     TRAIN_TRY(hipSetDevice(t->device));
     TRAIN_TRY(hipDeviceSynchronize());
     TRAIN_TRY(hipMemcpy2D(out_host, (size_t)width * sizeof(float), from, (size_t)ld * sizeof(float), (size_t)width * sizeof(float), (size_t)n_samples_total, hipMemcpyDeviceToHost));
@@ -306,12 +436,15 @@ int FlexBackend::activation(int layer, int64_t n_samples_total, float *out_host)
 }
 }   // namespace
 namespace ntx_train {
-// the architectures the flex render family takes (ntx_arch.h: find_variant) without parameter branches
-int flex_check(const ntx_model_desc *desc, TrainDims *dims) {
+// the architectures the flex render family takes (ntx_arch.h: find_variant): without parameter branches (ntx_trainer_create_flex), or --
+// branches: desc is an ntx_model_desc_ex -- with them, within the render side's limits (ntx_trainer_create_flex_ex)
+int flex_check(const ntx_model_desc *desc, TrainDims *dims, bool branches) {
     const bool nerf = desc->kind == NTX_MODEL_NERF;
+    if (branches && desc->kind != NTX_MODEL_PARAMNERF_EX)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: model kind %d (ntx_trainer_create_flex_ex takes an ntx_model_desc_ex, kind NTX_MODEL_PARAMNERF_EX)", desc->kind);
     if (desc->kind != NTX_MODEL_PARAMNERF && desc->kind != NTX_MODEL_NERF && desc->kind != NTX_MODEL_PARAMNERF_EX) return ntx_set_error(NTX_E_UNSUPPORTED, "training: model kind %d", desc->kind);
-    if (desc->kind == NTX_MODEL_PARAMNERF_EX && desc->n_geo + desc->n_app > 0 && reinterpret_cast<const ntx_model_desc_ex *>(desc)->param_depth != 0)
-        return ntx_set_error(NTX_E_UNSUPPORTED, "training: parameter branches (param_depth > 0) render but do not train");
+    if (!branches && desc->kind == NTX_MODEL_PARAMNERF_EX && desc->n_geo + desc->n_app > 0 && reinterpret_cast<const ntx_model_desc_ex *>(desc)->param_depth != 0)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training: parameter branches (param_depth > 0) train through ntx_trainer_create_flex_ex");
     if (desc->pos_encoding != NTX_POS_FOURIER || desc->n_pos != 3)
         return ntx_set_error(NTX_E_UNSUPPORTED, "the layer-by-layer trainer takes Fourier features on n_pos 3 (an IPE model trains in the 8 x 256 / skips [4] / color_depth 1 shape: ntx_trainer_create)");
     const int n_geo = nerf ? 0 : desc->n_geo, n_app = nerf ? 0 : desc->n_app, cd = nerf ? 0 : desc->color_depth;
@@ -324,17 +457,29 @@ int flex_check(const ntx_model_desc *desc, TrainDims *dims) {
         (n_geo + n_app > 0 && (desc->param_freq < 0 || desc->param_freq > 4)))
         return ntx_set_error(NTX_E_UNSUPPORTED, "training: n_parameters [%d,%d] / band counts %d %d %d (built: [g<=4, a<=8], bands <= 10 / 4 / 4)", n_geo, n_app, desc->pos_freq,
                              desc->dir_freq, desc->param_freq);
+    int pd = 0, pw = 0;
+    if (branches) {
+        const ntx_model_desc_ex *ex = reinterpret_cast<const ntx_model_desc_ex *>(desc);
+        if (ex->param_depth < 0 || ex->param_depth > ntx::FLEX_MAX_PARAM_DEPTH || (ex->param_depth > 0 && (ex->param_width < 2 || ex->param_width > 2 * ntx::BRANCH_K)))
+            return ntx_set_error(NTX_E_UNSUPPORTED, "training: param_depth %d param_width %d (built: param_depth 0..%d, param_width 2..%d)", ex->param_depth, ex->param_width,
+                                 ntx::FLEX_MAX_PARAM_DEPTH, 2 * ntx::BRANCH_K);
+        pd = n_geo + n_app > 0 ? ex->param_depth : 0;                        // a model without parameters has no branches (model.py:88, 96)
+        pw = pd > 0 ? ex->param_width : 0;
+    }
     const int pfq = n_geo + n_app > 0 ? desc->param_freq : 0;
     dims->desc = *desc; dims->desc.n_geo = n_geo; dims->desc.n_app = n_app; dims->desc.param_freq = pfq; dims->ipe = false;
-    dims->Kp = ntx::pos_map_m(ntx::dims_of(desc), 0); dims->Kd = ntx::dir_map_m(ntx::dims_of(desc));
-    dims->n_weights = FlexBackend().plan(desc);
+    if (branches) dims->desc.kind = NTX_MODEL_PARAMNERF;                     // (the handle's copy is the base struct alone: nothing may look behind it)
+    dims->param_depth = pd; dims->param_width = pw;
+    FlexBackend plan;
+    dims->n_weights = plan.plan(desc, pd, pw);
+    dims->Kp = plan.Kp; dims->Kd = plan.Kd;
     return NTX_OK;
 }
 
 int flex_backend_create(ntx_trainer *t) {
     FlexBackend *f = new FlexBackend();
     t->backend = f; f->t = t;
-    f->plan(&t->desc);
+    f->plan(&t->desc, t->param_depth, t->param_width);
     f->place();
     return t->mem.rc;
 }

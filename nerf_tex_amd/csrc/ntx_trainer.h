@@ -1,6 +1,6 @@
 // ntx_trainer.h -- what the units of a training step share on the host: the handle behind ntx_trainer_* (ntx_trainer.hip), the interface of
 // its two backends (ntx_backend_chain.hip: the 8 x 256 chain on ntx_train_device.h's kernels; ntx_backend_flex.hip: any other architecture
-// layer by layer), the owner of its device memory, and the launchers of the kernels more than one unit uses (no relocatable device code: a
+// layer by layer, parameter branches included), the owner of its device memory, and the launchers of the kernels more than one unit uses (no relocatable device code: a
 // kernel is launched by a host function of the unit that defines it).
 #pragma once
 #include "ntx_arch.h"   // the model's dimensions and the one view of its blob; ntx_set_error
@@ -52,13 +52,14 @@ struct Backend {
     virtual int activation(int layer, int64_t n_samples_total, float *out_host) = 0;   // ntx_trainer_activation, the arguments checked
 };
 // what an entry's architecture check makes of a descriptor
-struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; };
+struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; int param_depth, param_width; };   // param_*: the branches the model HAS (0 without parameters)
 using TLayer = ntx::BlobLayer;                    // offsets into the Keras-order blob (kernel [in][out], then bias)
 }   // namespace ntx_train
 
 struct ntx_trainer {
     int device = 0, cus = 256;
     ntx_model_desc desc{};
+    int param_depth = 0, param_width = 0;      // the parameter branches of an extended descriptor (ntx_trainer_create_flex_ex): the base struct has no room for them
     int Kp = 0, Kd = 0, P = 0;                 // features of pos_map / dir_map, parameters the model sees
     bool ipe = false; size_t n_weights = 0;    // ipe: an IntegratedPositionalEncoding model, a MipRenderer step
     long long cap = 0, cap_blocks = 0, cap_rays = 0;   // samples (blocks of 32 samples, rays) the buffers hold
@@ -78,7 +79,7 @@ namespace ntx_train {
 // common buffers exist (allocations go through t->mem; the caller looks at t->mem.rc)
 int chain_check(const ntx_model_desc *desc, TrainDims *dims);
 int chain_backend_create(ntx_trainer *t);
-int flex_check(const ntx_model_desc *desc, TrainDims *dims);
+int flex_check(const ntx_model_desc *desc, TrainDims *dims, bool branches = false);   // branches: ntx_trainer_create_flex_ex's domain (desc is an ntx_model_desc_ex)
 int flex_backend_create(ntx_trainer *t);
 // ntx_gemm.hip: C[i][j] = sum_p A'(i, p) B[p * ldb + j], A'(i, p) = a_kcontig ? A[i * lda + p] : A[p * lda + i]
 struct GemmArgs {

@@ -4,7 +4,7 @@
 // network: composite_loss_kernel (renderer.py:170-213 per ray, the ray's term of the loss and the adjoint of both), reduce_batch_kernel (the
 // weight gradients' partial sums added in a fixed order: a step is bit-reproducible), adam_kernel (train.py:49-52).
 // The network between the encoded rays and the composite is a backend's (ntx_trainer.h): the 8 x 256 chain of ntx_backend_chain.hip behind
-// ntx_trainer_create, the layer-by-layer step of ntx_backend_flex.hip behind ntx_trainer_create_flex.  Inference fuses the whole network into
+// ntx_trainer_create, the layer-by-layer step of ntx_backend_flex.hip behind ntx_trainer_create_flex / _flex_ex.  Inference fuses the whole network into
 // one kernel because nothing of it has to survive (ntx_device.h); a training step has to keep every layer's activations for the weight
 // gradients, and with 288 GB of HBM they are simply stored, once each.  Everything is float32 with float32 accumulation, like the
 // reference's TensorFlow graph.  gfx950 only.
@@ -196,15 +196,16 @@ __global__ void adam_kernel(float *__restrict__ w, const float *__restrict__ g, 
 }   // namespace ntx_train
 
 using namespace ntx_train;
-// Both create entries: the architecture check first (trainer_class_for in train.py asks with max_rays = 0 and counts on NTX_E_UNSUPPORTED
+// The create entries (kind 0: the chain, 1: layer by layer, 2: layer by layer with parameter branches): the architecture check first (trainer_class_for in train.py asks with max_rays = 0 and counts on NTX_E_UNSUPPORTED
 // before NTX_E_INVALID, and on no device being asked for before either), then the sizes, the device, the handle with the buffers and weights
 // every backend needs, and the backend.
-static int trainer_create(bool flex, const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
+static int trainer_create(int kind, const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
     if (!out) return ntx_set_error(NTX_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!desc || !weights) return ntx_set_error(NTX_E_INVALID, "desc / weights is NULL");
+    const bool flex = kind != 0;
     TrainDims dm{};
-    int rc = flex ? flex_check(desc, &dm) : chain_check(desc, &dm);
+    int rc = flex ? flex_check(desc, &dm, kind == 2) : chain_check(desc, &dm);
     if (rc != NTX_OK) return rc;
     if (max_rays < 1 || max_samples_per_ray < 2 || max_samples_per_ray > MAX_TRAIN_SAMPLES || max_rays * (int64_t)max_samples_per_ray > (int64_t)1 << 30)
         return ntx_set_error(NTX_E_INVALID, "max_rays / max_samples_per_ray out of range (samples per ray <= %d)", MAX_TRAIN_SAMPLES);
@@ -217,6 +218,7 @@ static int trainer_create(bool flex, const ntx_model_desc *desc, const float *we
     if (!flex && (rc = count_ok()) != NTX_OK) return rc;
     ntx_trainer *t = new ntx_trainer();
     t->device = device; t->desc = dm.desc; t->ipe = dm.ipe; t->P = dm.desc.n_geo + dm.desc.n_app; t->Kp = dm.Kp; t->Kd = dm.Kd; t->n_weights = p;
+    t->param_depth = dm.param_depth; t->param_width = dm.param_width;
     const long long M = (long long)max_rays * max_samples_per_ray, NB = (M + 31) / 32;
     t->cap = M; t->cap_rays = max_rays; t->cap_blocks = NB;
     DeviceMemory &mem = t->mem;
@@ -236,11 +238,14 @@ static int trainer_create(bool flex, const ntx_model_desc *desc, const float *we
 
 extern "C" {
 int ntx_trainer_create(const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
-    return trainer_create(false, desc, weights, n_floats, device, max_rays, max_samples_per_ray, out);
+    return trainer_create(0, desc, weights, n_floats, device, max_rays, max_samples_per_ray, out);
 }
 
 int ntx_trainer_create_flex(const ntx_model_desc *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
-    return trainer_create(true, desc, weights, n_floats, device, max_rays, max_samples_per_ray, out);
+    return trainer_create(1, desc, weights, n_floats, device, max_rays, max_samples_per_ray, out);
+}
+int ntx_trainer_create_flex_ex(const ntx_model_desc_ex *desc, const float *weights, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray, ntx_trainer **out) {
+    return trainer_create(2, desc ? &desc->base : nullptr, weights, n_floats, device, max_rays, max_samples_per_ray, out);
 }
 int ntx_trainer_destroy(ntx_trainer *t) { delete t; return NTX_OK; }
 size_t ntx_trainer_weight_count(const ntx_trainer *t) { return t ? t->n_weights : 0; }

@@ -14,8 +14,9 @@ with model + step + optimizer (train.py:55-57) that `Trainer.restore` resumes fr
 it), with FourierFeatures under the Renderer or -- an IntegratedPositionalEncoding model (n_pos 6) -- under the MipRenderer
 (renderer.py:356-473): three fused passes over the layer chain.  `FlexTrainer` trains every other Nerf / ParamNerf the renderer's flex family
 takes (FourierFeatures; depth 1..24, width 2..256, color_depth 0..4, skips below depth-1, no parameter branches) layer by layer: one
-contraction per Dense layer and pass (`ntx_trainer_create_flex`).  `trainer_for(model, ...)` picks between them, and `Trainer.from_config`,
-`CoarseFineTrainer` and `Train` build their trainers through it."""
+contraction per Dense layer and pass (`ntx_trainer_create_flex`); `BranchTrainer` is the same step for a ParamNerf with parameter branches
+(param_depth 1..4, param_width 2..128: `ntx_trainer_create_flex_ex`).  `trainer_for(model, ...)` picks between them, and
+`Trainer.from_config`, `CoarseFineTrainer` and `Train` build their trainers through it."""
 
 from __future__ import annotations
 
@@ -316,6 +317,35 @@ class FlexTrainer(Trainer):
         return out
 
 
+class BranchTrainer(FlexTrainer):
+    """`FlexTrainer` for a ParamNerf with parameter branches (model.py:88-101: `param_depth` Dense(param_width, relu) layers on the Fourier
+    features of the geometry parameters and, separately, of the appearance parameters; param_depth 0..4, param_width 2..128) behind
+    `ntx_trainer_create_flex_ex`.  The branches are evaluated per sample, their layers train like the trunk's, and their weights sit where
+    `get_weights()` has them.  With param_depth 0 (or a model without parameters) the step is `FlexTrainer`'s bit for bit."""
+
+    @staticmethod
+    def _create(desc_ref, *a):
+        desc = desc_ref._obj
+        desc.kind = _lib.KIND_PARAMNERF_EX                                       # the extended descriptor, also when param_depth is 0
+        return _lib.lib.ntx_trainer_create_flex_ex(C.byref(desc), *a)
+
+    def branch_widths(self):
+        """Widths of the branch ReLU layers in the order of the oracle's `branch_masks`: geometry layers (`activation` 32 + j), then
+        appearance layers (48 + j); a branch exists where the model has parameters of its kind."""
+        m = self.model
+        return [m.param_width] * (m.param_depth * ((m.n_geo > 0) + (m.n_app > 0)))
+
+    def activation(self, layer: int, n_samples_total: int):
+        """`FlexTrainer.activation`, and `layer` 32 + j / 48 + j: the kept output of layer j of the geometry / appearance branch,
+        [n_samples_total, param_width] float32 (tests)."""
+        import numpy as np
+        if not 32 <= int(layer) < 64:
+            return super().activation(layer, n_samples_total)
+        out = np.empty((int(n_samples_total), self.model.param_width), np.float32)
+        _lib.check(_lib.lib.ntx_trainer_activation(self._h, int(layer), int(n_samples_total), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+
 def _chain_takes(model) -> bool:
     """Whether `Trainer` (the fused chain, `ntx_trainer_create`) trains `model`: ParamNerf 8 x 256 / skips [4] / color_depth 1 with Fourier
     features or IPE and encodings of at most 96 features, or a narrower Fourier network that `_widened` pads into it."""
@@ -331,24 +361,27 @@ def _chain_takes(model) -> bool:
     return _widened(model) is not None and model.n_pos == 3
 
 
-def trainer_class_for(model):
+def trainer_class_for(model, branches: bool = False):
     """The class that trains `model`, without creating anything (no device is asked for): `Trainer` where the fused chain takes it,
-    `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise."""
+    `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise -- which is what a
+    model with parameter branches gets unless `branches` is set: then a model with param_depth > 0 and at least one parameter gets
+    `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it."""
     import numpy as np
     if _chain_takes(model):
         return Trainer
+    cls = BranchTrainer if branches and model.param_depth > 0 and model.n_params > 0 else FlexTrainer
     desc, h = model.desc(), C.c_void_p()
     blob = np.zeros(max(1, model.n_weight_floats()), np.float32)
     # the entry checks the architecture first (NTX_E_UNSUPPORTED) and max_rays = 0 next (NTX_E_INVALID), before anything is created
-    rc = _lib.lib.ntx_trainer_create_flex(C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, 0, 0, 0, C.byref(h))
+    rc = cls._create(C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, 0, 0, 0, C.byref(h))
     if rc != _lib.NTX_E_INVALID:                                                   # NTX_E_UNSUPPORTED, with the library's own words
         _lib.check(rc)
-    return FlexTrainer
+    return cls
 
 
 def trainer_for(model, **kw):
-    """`Trainer(model, **kw)` or `FlexTrainer(model, **kw)`, whichever `trainer_class_for` names."""
-    return trainer_class_for(model)(model, **kw)
+    """`Trainer(model, **kw)`, `FlexTrainer(model, **kw)` or `BranchTrainer(model, **kw)`, whichever `trainer_class_for(model, branches=True)` names."""
+    return trainer_class_for(model, branches=True)(model, **kw)
 
 
 class CoarseFineTrainer:

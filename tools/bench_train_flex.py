@@ -4,6 +4,7 @@ AlphaLoss(smape, mse) + Adam, timed with HIP events over whole steps:
     B  the same model through FlexTrainer      (B / A on one model is the ratio that matters)
     C  a plain Nerf 8 x 256 through FlexTrainer
     D  a ParamNerf [1, 6] of width 128, depth 4 through FlexTrainer
+    E  the carpet model with param_depth 2 (two Dense(128) layers per parameter branch) through BranchTrainer   (E / B: what the branches cost)
 A and B alternate twice in one process so that clock drift shows.
     python tools/bench_train_flex.py [--steps 20] [--warmup 5] [--only B] [--out profiles/train_flex/bench.json]
 One JSON line: per run ms a step, ray-samples/s and the fraction of the f32 matrix cores' peak the FLOPs a step needs take (bench.py's
@@ -50,13 +51,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--only", default=None, help="one of A B C D (a profiler's run)")
+    ap.add_argument("--only", default=None, help="one of A B C D E (a profiler's run)")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
     from nerf_tex_amd import synthetic
     from nerf_tex_amd.loss import AlphaLoss
     from nerf_tex_amd.model import Nerf, ParamNerf
-    from nerf_tex_amd.train import FlexTrainer, Trainer
+    from nerf_tex_amd.train import BranchTrainer, FlexTrainer, Trainer
     B, R, S = 4, 256, 256
     n = B * R
     f = synthetic.FAMILIES["carpet"]
@@ -71,8 +72,9 @@ def main():
     seeded = lambda m: (m.set_blob(synthetic.synthetic_weights(m.layer_table(), seed=0, dense_media=True)), m)[1]
     carpet = seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6])["model"])
     runs = {"A": (Trainer, carpet), "B": (FlexTrainer, carpet), "C": (FlexTrainer, seeded(Nerf(emb(10), emb(4))["model"])),
-            "D": (FlexTrainer, seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6], width=128, depth=4)["model"]))}
-    order = [a.only] if a.only else ["A", "B", "A", "B", "C", "D"]
+            "D": (FlexTrainer, seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6], width=128, depth=4)["model"])),
+            "E": (BranchTrainer, seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6], param_depth=2)["model"]))}
+    order = [a.only] if a.only else ["A", "B", "A", "B", "C", "D", "E", "B", "E"]
     out = {"what": "training step, 1024 rays x 256 samples, perturb, AlphaLoss(smape, mse) + Adam; HIP events", "steps": a.steps, "warmup": a.warmup, "runs": []}
     trainers = {}
     for key in order:
@@ -82,11 +84,14 @@ def main():
         batch = (d(ro), d(rd), d(t), d(params) if model.n_params else None, d(cone), d(color), d(alpha))
         sec = time_steps(trainers[key], batch, loss, a.steps, a.warmup, rays_per_param_row=R)
         fl = step_flops(model, n * S)
-        out["runs"].append({"run": key, "trainer": cls.__name__, "model": f"{'Nerf' if model.kind else 'ParamNerf'} {model.depth} x {model.width}", "ms_step": 1e3 * sec,
+        out["runs"].append({"run": key, "trainer": cls.__name__,
+                            "model": f"{'Nerf' if model.kind else 'ParamNerf'} {model.depth} x {model.width}" + (f" param_depth {model.param_depth}" if model.param_depth else ""), "ms_step": 1e3 * sec,
                             "ray_samples_per_s": n * S / sec, "gflop_step": fl / 1e9, "fraction_of_f32_mfma_peak": fl / sec / PEAK_F32_MFMA})
     ms = lambda k: [r["ms_step"] for r in out["runs"] if r["run"] == k]
     if ms("A") and ms("B"):
         out["B_over_A"] = float(np.mean(ms("B")) / np.mean(ms("A")))
+    if ms("B") and ms("E"):
+        out["E_over_B"] = float(np.mean(ms("E")) / np.mean(ms("B")[-len(ms("E")):]))      # the B runs next to the E runs
     line = json.dumps(out)
     print(line)
     if a.out:

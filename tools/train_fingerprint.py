@@ -1,7 +1,8 @@
 """A training step's bits, as hashes: one JSON line per case with the sha256 of the float32 loss, color_pred, alpha_pred and gradient vector of
 one `gradients_step`, then of the weights and both Adam moments after two more whole steps.  The cases are the smallest seeded batches that
 reach every path of the native training code (both backends, every forward-chain build, both encoders, the per-ray direction row, the
-2048-sample split, the composite weights of a coarse pass, the contraction alone).  A step is bit-reproducible, so two runs on one library
+2048-sample split, the composite weights of a coarse pass, the contraction alone; behind them the parameter branches of
+ntx_trainer_create_flex_ex, which a library without that entry cannot run: compare the lines in front of them).  A step is bit-reproducible, so two runs on one library
 print the same lines, and a change that only moves code prints what its parent prints:
     NERFTEX_LIB=<parent's libnerftex_hip.so> python tools/train_fingerprint.py > parent.jsonl
     python tools/train_fingerprint.py > new.jsonl && cmp parent.jsonl new.jsonl
@@ -67,10 +68,12 @@ def ipe(blur_idx):
     return fingerprint(tr, (ro, rd, t, params, cone, *targets(n, 2)), make_loss("alpha_smape")[1])
 
 
-def flex(arch_id, n=45, S=37, extended=False, **kw):
-    """`extended`: the same model through an ntx_model_desc_ex with param_depth 0 (kind NTX_MODEL_PARAMNERF_EX), which the C ABI takes: same bits"""
+def flex(arch_id, n=45, S=37, extended=False, entry_ex=False, **kw):
+    """`extended`: the same model through an ntx_model_desc_ex with param_depth 0 (kind NTX_MODEL_PARAMNERF_EX), which the C ABI takes: same bits;
+    `entry_ex`: through ntx_trainer_create_flex_ex (`BranchTrainer`), which takes param_depth 0 too: same bits again"""
     from nerf_tex_amd import _lib
-    from nerf_tex_amd.train import FlexTrainer
+    from nerf_tex_amd import train
+    FlexTrainer = train.BranchTrainer if entry_ex else train.FlexTrainer
     _, npar, kind, arch, fam = next(a for a in ARCHS if a[0] == arch_id)
     model, _, _ = make_model(npar, kind=kind, arch=arch, dense_media=True)
     if extended:
@@ -78,6 +81,16 @@ def flex(arch_id, n=45, S=37, extended=False, **kw):
         model.desc = lambda: _lib.ModelDesc(_lib.KIND_PARAMNERF_EX, *[getattr(plain(), f) for f, _ in _lib.ModelDesc._fields_[1:12]], 0, 128)
     tr = FlexTrainer(model, max_rays=n, n_samples=S, perturb=True, **kw)
     return fingerprint(tr, family_batch(fam, n, S, sum(npar)), make_loss("alpha_smape")[1])
+
+
+def branches(npar, arch, fam, n=45, S=37, **kw):
+    """A ParamNerf with parameter branches (param_depth > 0) through `BranchTrainer`"""
+    from nerf_tex_amd.train import BranchTrainer
+    from tests.train_branch_oracle import branch_batch
+    model, spec, _ = make_model(npar, arch=arch, dense_media=True)
+    tr = BranchTrainer(model, max_rays=n, n_samples=S, perturb=True, **kw)
+    ro, rd, t, cone, params, color, alpha = branch_batch(3, n, spec, fam)
+    return fingerprint(tr, (ro, rd, t, params, cone, color, alpha), make_loss("alpha_smape")[1])
 
 
 def coarse_fine():
@@ -124,7 +137,15 @@ CASES = [
     ("flex coarse + fine Nerfs 16x(16+16)", coarse_fine),                                                                 # ntx_trainer_composite_weights
     ("gemm 300x200x77 A k-contiguous", lambda: gemm(1, 300, 200, 77)),
     ("gemm 337x256x1000 A transposed", lambda: gemm(0, 337, 256, 1000)),
+    # ntx_trainer_create_flex_ex: the lines above are what a library from before it prints
+    ("flex w128_d4 grass_filtered 41x70 blur0, ntx_trainer_create_flex_ex", lambda: flex("w128_d4", 41, 70, blur_idx=0, entry_ex=True)),       # param_depth 0 through the new entry
+    ("branches geometry only (3,0) d5 [2] pd2", lambda: branches((3, 0), dict(depth=5, skips=[2], param_depth=2), "carpet")),
+    ("branches appearance only (0,5) d5 [2] pd2", lambda: branches((0, 5), dict(depth=5, skips=[2], param_depth=2), "carpet")),
+    ("branches both (4,8) d6 w200 [0,4] cd2 pd4 pw100", lambda: branches((4, 8), dict(depth=6, width=200, skips=[0, 4], color_depth=2, param_depth=4, param_width=100), "carpet")),
+    ("branches (2,3) d4 w128 [1,2] cd0 pd3 pw64 41x70 blur0 noise", lambda: branches((2, 3), dict(depth=4, width=128, skips=[1, 2], color_depth=0, param_depth=3, param_width=64),
+                                                                                 "grass_filtered", 41, 70, blur_idx=0, raw_noise_std=0.1)),     # the branch input differs per sample
 ]
+SAME_AS = (", extended descriptor", ", ntx_trainer_create_flex_ex")               # a case named "<other case><suffix>" has to print that case's hashes
 
 
 def main():
@@ -133,8 +154,9 @@ def main():
         try:
             lines[name] = run()
             print(json.dumps({"case": name, **lines[name]}), flush=True)
-            if name.endswith(", extended descriptor") and lines[name] != lines[name[:-len(", extended descriptor")]]:
-                raise ValueError("an extended descriptor with param_depth 0 trains to other bits than the plain one")
+            for suffix in SAME_AS:
+                if name.endswith(suffix) and lines[name] != lines[name[:-len(suffix)]]:
+                    raise ValueError(f"param_depth 0{suffix} trains to other bits than through the plain descriptor and ntx_trainer_create_flex")
         except Exception:                                   # (nothing more is started on a device that may just have faulted)
             print(json.dumps({"case": name, "error": traceback.format_exc(limit=3)}), flush=True)
             return 1
