@@ -91,12 +91,15 @@ def _loss(loss, color_true, alpha_true, c, a):
 
 
 def composite_gradients(raw_rgb, sigma, z, rays_d, color_true, alpha_true, loss, map_exr=False, composite_bkgd=False, bkgd=(1., 1., 1.), noise=None,
-                        dtype=torch.float64):
+                        dtype=torch.float64, mip=False):
     """The Renderer's composite and the loss alone under autograd: (loss, color_pred, alpha_pred, dL/d raw_rgb [n, S, 3], dL/d sigma [n, S]) for GIVEN raw
-    network outputs -- what a hand-written adjoint of renderer.py:170-213 + loss.py is compared with, apart from the network's own rounding."""
+    network outputs -- what a hand-written adjoint of renderer.py:170-213 + loss.py is compared with, apart from the network's own rounding.
+    `mip`: the MipRenderer's composite (renderer.py:439-473): `z` [n, S + 1] holds the segment edges and a sample's length is its segment's."""
     t_ = lambda a: None if a is None else torch.tensor(np.asarray(a), dtype=dtype)
     rgb = torch.tensor(np.asarray(raw_rgb), dtype=dtype, requires_grad=True); sg = torch.tensor(np.asarray(sigma), dtype=dtype, requires_grad=True)
-    c, a = composite(rgb, sg, fourier_dists(t_(z), t_(rays_d)), map_exr, composite_bkgd, bkgd, None, t_(noise))
+    if np.shape(z)[-1] != sg.shape[-1] + (1 if mip else 0):
+        raise ValueError(f"{np.shape(z)[-1]} depths for {sg.shape[-1]} samples (mip={mip})")
+    c, a = composite(rgb, sg, (mip_dists if mip else fourier_dists)(t_(z), t_(rays_d)), map_exr, composite_bkgd, bkgd, None, t_(noise))
     val = _loss(loss, t_(color_true), t_(alpha_true), c, a)
     val.backward()
     return float(val.detach()), c.detach().numpy(), a.detach().numpy(), rgb.grad.numpy(), sg.grad.numpy()

@@ -13,7 +13,7 @@ import pytest
 from oracle import nerftex_oracle as orc
 from oracle import train_oracle as tro
 from tests.common import make_model
-from tests.train_common import LOSSES, layer_slices, make_loss, rel_linf, restated_step, step_pred                  # (tests/_dp_train_worker.py and tools/dev/ take them from here)
+from tests.train_common import LOSSES, adjoint_errors, layer_slices, make_loss, rel_linf, restated_step, step_pred                  # (tests/_dp_train_worker.py and tools/dev/ take them from here)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -224,19 +224,10 @@ def step_errors(model, spec, wts, fam, n, S, loss_name, perturb=False, bkgd=Fals
                layers={nm: lerr(sl) for nm, sl in layer_slices(spec)} if gmax > 0 else {"all": float(np.abs(got).max())},
                finite=bool(np.isfinite(got).all()), got=got, want=flat, gmax=gmax, alpha_pred=want_pred[:, 3], sigma=sg, z=z)
     out["e_grad"] = max(out["layers"].values())
-    # the composite's adjoint on its own: dL/d raw colour, dL/d raw density as the step left them against float64 autograd of the composite and
-    # the loss on the step's OWN float32 network outputs (the network's rounding, which exp(-sigma dist) amplifies by sigma dist, stays out)
-    hit = ~miss
-    raw, dg = tr.activation(11, M).reshape(n, S, 3), tr.activation(30, M).reshape(n, S, 4)
-    if hit.any():
-        # the loss is a mean over ALL rays of the batch: the hit rays' share of it, scaled back
-        sub = lambda x: None if x is None else np.asarray(x)[hit]
-        _, _, _, d_rgb, d_sg = tro.composite_gradients(raw[hit], sg[hit], z[hit], rd[hit], color[hit], alpha[hit], okw, composite_bkgd=bkgd, bkgd=(1., .5, .25), noise=sub(noise))
-        scale = hit.sum() / n
-        # (the ReLU of the density: autograd's own branch on the same float32 value, so the patterns agree)
-        out["e_dsigma"] = rel_linf(dg[hit][..., 3], d_sg * scale) if np.abs(d_sg).max() > 0 else float(np.abs(dg[hit][..., 3]).max())
-        out["e_drgb"] = rel_linf(dg[hit][..., :3], d_rgb * scale) if np.abs(d_rgb).max() > 0 else float(np.abs(dg[hit][..., :3]).max())
-        out["dsigma_max"] = float(np.abs(d_sg).max() * scale)
+    # the composite's adjoint on its own, on the step's OWN float32 network outputs (tests/train_common.py adjoint_errors)
+    if (~miss).any():
+        adj = adjoint_errors(tr, rd, z, color, alpha, okw, bkgd=bkgd, bkgd_color=(1., .5, .25), noise=noise, miss=miss)
+        out.update(e_dsigma=adj["e_dsigma"], e_drgb=adj["e_drgb"], dsigma_max=adj["dsigma_max"])
     if floors:
         f = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, dtype=torch.float32, **kw)
         out["floor_pred"] = orc.rel_linf(f.pred, want_pred)

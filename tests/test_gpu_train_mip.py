@@ -9,7 +9,7 @@ import pytest
 
 from oracle import nerftex_oracle as orc
 from tests.common import make_model
-from tests.train_common import make_loss, mip_batch, restated_step, targets
+from tests.train_common import adjoint_errors, make_loss, mip_batch, restated_step, targets
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -36,14 +36,19 @@ def check_mip_step(n, S, blur_idx, perturb, loss_name, noise_std=0.0, miss=(), b
     want = restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, seed=seed, perturb=perturb, noise_std=noise_std, miss=missed, blur_idx=blur_idx,
                          bkgd=bkgd, bkgd_color=BKGD, chunk_rays=chunk_rays)
     cp, ap = cp.cpu().numpy(), ap.cpu().numpy()
-    M = n * S
     assert abs(float(val.item()) - want.loss) <= 1e-4 * abs(want.loss) + 1e-7, (float(val.item()), want.loss)
     assert orc.rel_linf(np.concatenate([cp, ap[:, None]], -1), want.pred) <= 1e-4
     assert np.isfinite(want.got).all() and np.abs(want.grad).max() > 1e-6
     assert max(want.layers.values()) <= 1e-4, {k: v for k, v in want.layers.items() if v > 1e-5}
+    # the composite's adjoint on its own, through the segments' lengths (tests/train_common.py adjoint_errors): the chain trainer's bars
+    # (tests/test_gpu_train.py test_saturated_rays_keep_their_gradient), or four times what float32 autograd of the same composite makes
+    # of the step's raw outputs, as check_gradients' floor check has it
+    e = adjoint_errors(tr, rd, want.z, color, alpha, okw, bkgd=bkgd, bkgd_color=BKGD, noise=want.noise, miss=missed, floors=True)
+    print(f"mip adjoint n {n} S {S}: drgb {e['e_drgb']:.2e} (float32 {e['f_drgb']:.2e}) dsigma {e['e_dsigma']:.2e} (float32 {e['f_dsigma']:.2e})")
+    assert e["e_drgb"] <= max(5e-6, 4 * e["f_drgb"]) and e["e_dsigma"] <= max(5e-5, 4 * e["f_dsigma"]), (e["e_drgb"], e["f_drgb"], e["e_dsigma"], e["f_dsigma"])
     if missed.any():                                                              # 0 / the background, and nothing comes back from them
         assert (ap[missed] == 0).all() and (cp[missed] == (np.asarray(BKGD, F) if bkgd else 0)).all()
-        adj = tr.activation(30, M).reshape(n, S, 4)
+        adj = e["adj"]
         assert (adj[missed] == 0).all() and np.abs(adj[~missed]).max() > 0
     return tr
 

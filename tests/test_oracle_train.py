@@ -6,6 +6,7 @@ import pytest
 
 from oracle import nerftex_oracle as orc
 from oracle import train_oracle as tro
+from tests.train_common import LOSSES, make_loss
 
 torch = pytest.importorskip("torch")
 F = np.float32
@@ -66,6 +67,73 @@ def test_autograd_matches_finite_differences(loss):
     wt = [torch.tensor(x) for x in w]
     pos = torch.tensor(ro)[:, None, :] + torch.tensor(rd)[:, None, :] * torch.tensor(z)[:, :, None]
     assert val == pytest.approx(float(tro.step_gradients(w, spec, ro, rd, z, par, cone, ct, at, loss, blur_idx=0, composite_bkgd=True, bkgd=(1., .5, .2), noise=noise)[0]))
+
+
+@pytest.mark.parametrize("name", sorted(LOSSES))
+def test_loss_descriptor_carries_what_the_oracle_dict_says(name):
+    """Both sides of a `LOSSES` entry describe ONE loss: the `ntx_loss_desc` of the product's object holds the kind, the functions, gamma and
+    the two mask switches of the oracle's dict, with the reference's defaults where the dict is silent (loss.py:25: gamma 1, filter_color_loss,
+    use_hard_mask, and no alpha_loss_fn means loss_fn)."""
+    import ctypes, inspect
+    from nerf_tex_amd import _lib
+    okw, loss = make_loss(name)
+    d, fn = loss.desc(), {"mse": _lib.LOSS_MSE, "smape": _lib.LOSS_SMAPE}
+    assert d.size == ctypes.sizeof(_lib.LossDesc) and d.kind == {"nerf": _lib.LOSS_NERF, "alpha": _lib.LOSS_ALPHA}[okw["kind"]]
+    assert d.loss_fn == fn[okw["loss_fn"]]
+    if okw["kind"] == "nerf":
+        assert set(okw) == {"kind", "loss_fn"}
+        return
+    full = {k: p.default for k, p in inspect.signature(tro.alpha_loss).parameters.items() if p.default is not inspect.Parameter.empty}
+    assert set(okw) - {"kind"} <= set(full)
+    full.update({k: v for k, v in okw.items() if k != "kind"})
+    assert d.alpha_loss_fn == fn[full["alpha_loss_fn"] or full["loss_fn"]]
+    assert d.gamma == np.float32(full["gamma"]) and d.filter_color_loss == int(full["filter_color_loss"]) and d.use_hard_mask == int(full["use_hard_mask"])
+
+
+def test_loss_names_keep_their_meaning():
+    """tools/dev/soak_train.py and tests/_dp_train_worker.py read the first three by name; the rest are the settings the GPU tests add."""
+    assert LOSSES["alpha_smape"][0] == dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse")
+    assert LOSSES["alpha_mse_soft"][0] == dict(kind="alpha", loss_fn="mse", gamma=0.5, use_hard_mask=False) and LOSSES["nerf_mse"][0] == dict(kind="nerf", loss_fn="mse")
+    assert {"alpha_smape_smape", "alpha_mse_unfiltered", "alpha_smape_soft_g2", "alpha_mse_hard_g3", "nerf_smape"} <= set(LOSSES)
+    assert "alpha_loss_fn" not in LOSSES["alpha_smape_smape"][0] and "alpha_loss_fn" not in LOSSES["alpha_smape_smape"][1]      # the default is the case
+    u = LOSSES["alpha_mse_unfiltered"][0]
+    assert (u["loss_fn"], u["alpha_loss_fn"], u["gamma"], u["filter_color_loss"]) == ("mse", "smape", 0.25, False)
+
+
+@pytest.mark.parametrize("map_exr,bkgd", [(False, False), (True, True)])
+@pytest.mark.parametrize("name", sorted(LOSSES))
+def test_composite_gradients_match_finite_differences(name, map_exr, bkgd):
+    """`tro.composite_gradients` -- what the GPU composite's hand-written adjoint is held to (tests/test_gpu_train_composite.py) -- against central
+    differences in float64 at 3 rays x 5 samples, for every loss setting, with the sigmoid and with elu + 1 on raw colours either side of 0,
+    with and without the background term, under the density regulariser, through the Renderer's sample distances and through the
+    MipRenderer's segment lengths.  One alpha target is 0 (the masks), densities lie either side of the ReLU."""
+    okw = LOSSES[name][0]
+    n, S = 3, 5
+    rng = np.random.default_rng(7)
+    raw = rng.normal(size=(n, S, 3)) * 1.5
+    sg = rng.normal(size=(n, S)) * 4 + 2
+    noise = 0.1 * rng.normal(size=(n, S))
+    sg[np.abs(sg + noise) < 1e-2] = 0.5                                           # off the ReLU's kink by more than the step
+    rd = rng.normal(size=(n, 3))
+    ct, at = rng.uniform(0, 1, size=(n, 3)), np.asarray([0.7, 0.0, 0.4])
+    assert (raw > 0).any() and (raw < 0).any() and (sg + noise > 0).any() and (sg + noise < 0).any()
+    for mip in (False, True):
+        z = np.sort(rng.uniform(0.5, 1.5, size=(n, S + mip)), -1)
+        kw = dict(map_exr=map_exr, composite_bkgd=bkgd, bkgd=(1., .5, .2), noise=noise, mip=mip)
+        val, c, a, d_rgb, d_sg = tro.composite_gradients(raw, sg, z, rd, ct, at, okw, **kw)
+        assert 0.05 < a.max() < 0.999999 and np.abs(d_rgb).max() > 1e-4 and np.abs(d_sg).max() > 1e-4
+        other = tro.composite_gradients(raw, sg, z[:, :S] if mip else np.concatenate([z, z[:, -1:] + 0.3], -1), rd, ct, at, okw, **dict(kw, mip=not mip))[0]
+        assert abs(val - other) > 1e-6                                            # the two renderers' lengths are not the same composite
+        f = lambda r, s: tro.composite_gradients(r, s, z, rd, ct, at, okw, **kw)[0]
+        h = 1e-6
+        for idx in np.ndindex(n, S, 3):
+            rp, rm = raw.copy(), raw.copy(); rp[idx] += h; rm[idx] -= h
+            assert (f(rp, sg) - f(rm, sg)) / (2 * h) == pytest.approx(d_rgb[idx], rel=2e-5, abs=1e-9), (mip, idx)
+        for idx in np.ndindex(n, S):
+            sp, sm = sg.copy(), sg.copy(); sp[idx] += h; sm[idx] -= h
+            assert (f(raw, sp) - f(raw, sm)) / (2 * h) == pytest.approx(d_sg[idx], rel=2e-5, abs=1e-9), (mip, idx)
+    with pytest.raises(ValueError):
+        tro.composite_gradients(raw, sg, z, rd, ct, at, okw, mip=False)           # S + 1 depths are a mip step's
 
 
 def _dp_worker(rank, world, port, q):

@@ -20,7 +20,15 @@ def rel_linf(got, want):
 
 LOSSES = {"alpha_smape": (dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse"), dict(loss_fn="network.loss.smape", alpha_loss_fn="network.loss.mse")),
           "alpha_mse_soft": (dict(kind="alpha", loss_fn="mse", gamma=0.5, use_hard_mask=False), dict(loss_fn="network.loss.mse", gamma=0.5, use_hard_mask=False)),
-          "nerf_mse": (dict(kind="nerf", loss_fn="mse"), dict(loss_fn="network.loss.mse"))}
+          "nerf_mse": (dict(kind="nerf", loss_fn="mse"), dict(loss_fn="network.loss.mse")),
+          # AlphaLoss(loss_fn=smape) as written: no alpha_loss_fn means loss_fn (loss.py:25)
+          "alpha_smape_smape": (dict(kind="alpha", loss_fn="smape"), dict(loss_fn="network.loss.smape")),
+          "alpha_mse_unfiltered": (dict(kind="alpha", loss_fn="mse", alpha_loss_fn="smape", gamma=0.25, filter_color_loss=False),
+                                   dict(loss_fn="network.loss.mse", alpha_loss_fn="network.loss.smape", gamma=0.25, filter_color_loss=False)),
+          "alpha_smape_soft_g2": (dict(kind="alpha", loss_fn="smape", alpha_loss_fn="mse", gamma=2.0, use_hard_mask=False),
+                                  dict(loss_fn="network.loss.smape", alpha_loss_fn="network.loss.mse", gamma=2.0, use_hard_mask=False)),
+          "alpha_mse_hard_g3": (dict(kind="alpha", loss_fn="mse", gamma=3.0), dict(loss_fn="network.loss.mse", gamma=3.0)),
+          "nerf_smape": (dict(kind="nerf", loss_fn="smape"), dict(loss_fn="network.loss.smape"))}
 
 
 def make_loss(name):
@@ -54,8 +62,23 @@ def mip_batch(n, P_in, seed=0):
     return ro, rd, t, cone, params
 
 
+def step_depths(t, edges, seed, perturb, miss=None):
+    """The depths a step places itself between t (renderer.py:101-111; `edges` = S, or the S + 1 segment edges of an IPE trainer, :374-383),
+    with perturb the product's Philox jitter under `seed`; the rays of `miss` at z = inf."""
+    tf = np.where(np.isfinite(t), t, 0).astype(F)
+    z = (orc.z_values_perturbed(tf, edges, seed, F) if perturb else orc.z_values(tf, edges, F)).copy()
+    if miss is not None:
+        z[np.asarray(miss, bool)] = np.inf
+    return z
+
+
+def step_noise(n, S, seed, noise_std):
+    """The density regulariser's draws of a step (renderer.py:190-192, keyed like the jitter by (seed, ray, sample)), or None."""
+    return noise_std * orc.noise_normals(n, S, seed, dtype=F).astype(np.float64) if noise_std > 0 else None
+
+
 def restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, *, seed, perturb, noise_std=0.0, miss=None, blur_idx=None, bkgd=False,
-                  bkgd_color=BKGD, chunk_rays=None, workers=1, free=False, dtype=torch.float64):
+                  bkgd_color=BKGD, chunk_rays=None, workers=1, free=False, dtype=torch.float64, S=None, map_exr=False):
     """The step `tr.gradients_step(..., seed=seed)` has just taken, restated: the sample depths the kernel placed itself (renderer.py:101-111:
     S of them, or the S + 1 segment edges of an IPE trainer, :374-383; with perturb the product's Philox jitter) and the density
     regulariser's draws (renderer.py:190-192, keyed like the jitter by (seed, ray, sample)), the rays of `miss` at z = inf, through
@@ -63,20 +86,17 @@ def restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, *, 
     step kept (a pre-activation within rounding of zero falls on either side of its ReLU depending on summation order -- in TensorFlow's
     float32 as much as here), the density's with the noise added.
     Returns the oracle's `loss`, `pred` = [color | alpha] and flat gradient `grad`, the trainer's `got`, `layers` = rel-Linf of every
-    layer's kernel and bias against its own largest entry, and `z`, `noise`, `masks`."""
-    n, S = len(t), tr.n_samples
+    layer's kernel and bias against its own largest entry, and `z`, `noise`, `masks`.  `S`: the step's own `n_samples` where it was not the
+    trainer's; `map_exr`: the trainer's."""
+    n, S = len(t), S or tr.n_samples
     miss = np.zeros(n, bool) if miss is None else np.asarray(miss, bool)
-    edges = S + 1 if spec.pos_encoding == "ipe" else S
-    tf = np.where(np.isfinite(t), t, 0).astype(F)
-    z = orc.z_values_perturbed(tf, edges, seed, F) if perturb else orc.z_values(tf, edges, F)
-    z = z.copy(); z[miss] = np.inf
-    noise = noise_std * orc.noise_normals(n, S, seed, dtype=F).astype(np.float64) if noise_std > 0 else None
+    z, noise = step_depths(t, S + 1 if spec.pos_encoding == "ipe" else S, seed, perturb, miss), step_noise(n, S, seed, noise_std)
     torch.cuda.synchronize()
     masks = sigma_mask = None
     if not free:
         masks = [tr.activation(k, n * S) > 0 for k in list(range(8)) + [8, 9]]              # bool: 67 MB each at the configs' batch
         sigma_mask = (tr.activation(10, n * S).reshape(n, S) + (0 if noise is None else noise.astype(F))) > 0
-    val, c, a, g = tro.step_gradients(wts, spec, ro, rd, z, params, np.nan_to_num(cone), color, alpha, okw, blur_idx=blur_idx, composite_bkgd=bkgd,
+    val, c, a, g = tro.step_gradients(wts, spec, ro, rd, z, params, np.nan_to_num(cone), color, alpha, okw, blur_idx=blur_idx, map_exr=map_exr, composite_bkgd=bkgd,
                                       bkgd=bkgd_color, dtype=dtype, masks=masks, sigma_mask=sigma_mask, noise=noise, chunk_rays=chunk_rays, workers=workers)
     got, flat = tr.gradients(), np.concatenate([x.ravel() for x in g])
     assert flat.size == got.size == tr.n_weights
@@ -87,3 +107,68 @@ def restated_step(tr, spec, wts, ro, rd, t, params, cone, color, alpha, okw, *, 
 def step_pred(color_pred, alpha_pred):
     """[color | alpha] of a `gradients_step`'s GPU tensors."""
     return np.concatenate([color_pred.cpu().numpy(), alpha_pred.cpu().numpy()[:, None]], -1)
+
+
+def raw_outputs(tr, n, S):
+    """(raw colour [n, S, 3], raw density [n, S]) the last step kept: slots 11 / 10 of a chain or IPE handle, 65 / 64 of a layer-by-layer one."""
+    flex = hasattr(tr, "relu_widths")
+    return tr.activation(65 if flex else 11, n * S).reshape(n, S, 3), tr.activation(64 if flex else 10, n * S).reshape(n, S)
+
+
+def adjoint_errors(tr, rd, z, color, alpha, okw, *, map_exr=False, bkgd=False, bkgd_color=BKGD, noise=None, miss=None, floors=False):
+    """The composite's adjoint on its own, beside a chain or IPE `Trainer` that has just stepped (a layer-by-layer handle keeps no slot 30):
+    dL/d raw colour, dL/d raw density as the step left them (`activation` 30) against float64 autograd of the composite and the loss
+    (`tro.composite_gradients`) on the step's OWN float32 network outputs -- the network's rounding, which exp(-sigma dist) amplifies by
+    sigma dist, stays out.  `z`: the depths the step used ([n, S], an IPE trainer's [n, S + 1] segment edges), `noise` [n, S] the density
+    regulariser's draws, `miss` the rays at t = inf.
+    Returns `e_drgb`, `e_dsigma` (rel-Linf over the hit rays; the absolute maximum where the oracle's gradient vanishes), `dsigma_max`, the
+    kernel's `adj` [n, S, 4] and the oracle's `want` [n, S, 4] (rows of missed rays 0), the oracle's `loss` and `pred` = [color | alpha] over
+    ALL rays (missed ones predict 0 / the background: renderer.py:58-86), and ray by ray `ray_drgb`, `ray_dsigma`: a hit ray's error relative to
+    that ray's own largest float64 entry, NaN where the oracle -- alone -- leaves the ray out because its largest entry is below 1e-3 of the
+    batch's (`left_out` = how many hit rays that is, the larger of the two counts).  `floors`: the same figures (`f_drgb`, `f_dsigma`,
+    `f_ray_drgb`, `f_ray_dsigma`, `f_loss`, `f_pred`) for float32 torch autograd of the same composite and loss: what float32 itself does
+    on these inputs."""
+    z = np.asarray(z)
+    n, mip = z.shape[0], bool(getattr(tr, "mip", False))
+    S = z.shape[1] - (1 if mip else 0)
+    M = n * S
+    miss = np.zeros(n, bool) if miss is None else np.asarray(miss, bool)
+    hit = ~miss
+    (raw, sg), dg = raw_outputs(tr, n, S), tr.activation(30, M).reshape(n, S, 4)
+    out = dict(adj=dg, hit=hit)
+    if not hit.any():
+        return out
+    # the loss is a mean over ALL rays of the batch: the hit rays' share of it, scaled back
+    sub = lambda x: None if x is None else np.asarray(x)[hit]
+    scale = hit.sum() / n
+
+    def oracle(dtype):
+        _, c, a, d_rgb, d_sg = tro.composite_gradients(raw[hit], sg[hit], z[hit], rd[hit], color[hit], sub(alpha), okw, map_exr=map_exr, composite_bkgd=bkgd,
+                                                       bkgd=bkgd_color, noise=sub(noise), dtype=dtype, mip=mip)
+        want = np.zeros((n, S, 4)); want[hit, :, :3] = d_rgb * scale; want[hit, :, 3] = d_sg * scale
+        pred = np.zeros((n, 4)); pred[hit, :3] = c; pred[hit, 3] = a
+        if bkgd:
+            pred[miss, :3] = np.asarray(bkgd_color, np.float64)
+        t64 = lambda x: None if x is None else torch.tensor(np.asarray(x), dtype=torch.float64)
+        val = float(tro._loss(okw, t64(color), t64(alpha), t64(pred[:, :3]), t64(pred[:, 3])))
+        return want, pred, val
+
+    def errors(got, want):
+        res = {}
+        for key, sl in (("drgb", np.s_[..., :3]), ("dsigma", np.s_[..., 3])):
+            g, w = got[hit][sl].reshape(hit.sum(), -1), want[hit][sl].reshape(hit.sum(), -1)
+            # (the ReLU of the density: autograd's own branch on the same float32 value, so the patterns agree)
+            res["e_" + key] = rel_linf(g, w) if np.abs(w).max() > 0 else float(np.abs(g).max())
+            top = np.abs(w).max(1)
+            keep = top >= 1e-3 * max(top.max(), 1e-300)
+            res["ray_" + key] = np.where(keep, np.abs(g - w).max(1) / np.where(keep, top, 1.0), np.nan)
+        return res
+
+    want, pred, val = oracle(torch.float64)
+    out.update(errors(dg.astype(np.float64), want), want=want, pred=pred, loss=val, dsigma_max=float(np.abs(want[..., 3]).max()))
+    out["left_out"] = int(max(np.isnan(out["ray_drgb"]).sum(), np.isnan(out["ray_dsigma"]).sum()))
+    if floors:
+        want32, pred32, val32 = oracle(torch.float32)
+        out.update({"f_" + k[2:] if k.startswith("e_") else "f_" + k: v for k, v in errors(want32, want).items()})
+        out["f_pred"], out["f_loss"] = rel_linf(pred32, pred), abs(val32 - val) / (abs(val) + 1e-7)
+    return out
