@@ -607,6 +607,30 @@ int ntx_trainer_create_flex(const ntx_model_desc *desc, const float *weights_hos
  * that of appearance branch layer j, each [n_samples_total][param_width]; NTX_E_INVALID for a branch the model does not have. */
 int ntx_trainer_create_flex_ex(const ntx_model_desc_ex *desc, const float *weights_host, size_t n_floats, int device, int64_t max_rays, int max_samples_per_ray,
                                ntx_trainer **out);
+/* dL/d params of a training step (ABI v7, appended): the gradient of the step's loss with respect to the material parameters -- the inverse
+ * use of a ParamNerf, fitting parameters to target images with the weights fixed.  For a handle of ntx_trainer_create_flex or
+ * ntx_trainer_create_flex_ex whose model has parameters (n_geo + n_app > 0).  mode 0: off (the default; nothing about the handle or its
+ * steps changes, nothing is placed).  mode 1: every following ntx_train_step_gradients also leaves dL/d params; loss, predictions and weight
+ * gradients stay bit for bit what they are without it.  mode 2: parameters only -- as mode 1, but no weight gradient is contracted or
+ * reduced and the trainer's gradient buffer is left untouched; ntx_trainer_adam_step, ntx_trainer_allreduce_gradients and
+ * ntx_trainer_stash_gradients return NTX_E_INVALID until the mode is 0 or 1 again.  Buffers are placed at the first enable, for the trainer's
+ * capacity.  NTX_E_UNSUPPORTED: a handle of ntx_trainer_create (the fused chain stops at the encoded inputs; the layer-by-layer entries take
+ * the same model).  NTX_E_INVALID: a model without parameters (a Nerf, n_parameters [0, 0]), a mode outside 0..2.
+ * What is differentiated: the parameter rows `params` of the step, through FourierFeatures(parameters) (identity, sin and cos rows of every
+ * band, at the value the encoder fed) and, for blur_idx, through its product with the sample's cone_scale * z (renderer.py:155-158), into
+ * every layer that reads the parameter features: trunk layer 0 and the layers behind a skip (geometry), the first layer that reads dir_map
+ * (appearance) -- or the first layer of each parameter branch when param_depth > 0.  Positions and directions take no gradient.
+ * The order of the sums: the readers' terms in descending layer order; the samples of a ray in a fixed order of the ray's own (64 interleaved
+ * partial sums, then a butterfly); the rays of a parameter row r / rays_per_param_row in ascending ray order.  None depends on the
+ * trainer's capacity or on a launch's grid: a step's parameter gradients are bit-reproducible.  A ray with tnear_far = inf contributes
+ * exactly 0, whatever its cone_scale holds (NaN included).
+ * Out of scope: the parameters of an IPE model (it trains on the chain only), of a coarse + fine pair (two steps: add the two results), and
+ * an all-reduce of parameter gradients across ranks. */
+int ntx_trainer_enable_param_gradients(ntx_trainer *t, int mode);
+/* Where the last step left them: DEVICE memory of the trainer's device, grad_dev[rows][n_params] with rows = ceil(n_rays /
+ * rays_per_param_row) of that step and n_params = n_geo + n_app, geometry columns first; written in the step's stream order, valid until
+ * the next step.  NTX_E_INVALID when the mode is 0 or no step has run since it was enabled. */
+int ntx_trainer_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *rows, int *n_params);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,9 @@ keys, reachable by dotted path through the same `{'module': ...}` config convent
 runs in hand-written HIP kernels behind the C ABI of `include/nerftex.h`, loaded with ctypes
 (`_lib.py`); PyTorch only owns device buffers, streams and `torch.distributed`.
 
+`nerf_tex_amd.train` is the reference's training step on the same kernels' terms; `nerf_tex_amd.fit.ParameterFitter` is its inverse use:
+the material parameters that reproduce target images, with the weights fixed.
+
 There is no CPU fallback: modules that compute import `_lib`, which raises if
 `libnerftex_hip.so` is not built.
 """

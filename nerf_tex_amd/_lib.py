@@ -161,6 +161,8 @@ SYMBOLS = {
     "ntx_instancer_model_input": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_uint64, _op] + [_vp] * 12),
     "ntx_trainer_create_flex": (C.c_int, [C.POINTER(ModelDesc), _fp, C.c_size_t, C.c_int, C.c_int64, C.c_int, C.POINTER(_vp)]),
     "ntx_trainer_create_flex_ex": (C.c_int, [C.POINTER(ModelDesc), _fp, C.c_size_t, C.c_int, C.c_int64, C.c_int, C.POINTER(_vp)]),
+    "ntx_trainer_enable_param_gradients": (C.c_int, [_vp, C.c_int]),
+    "ntx_trainer_param_gradients": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
 }
 
 
@@ -190,6 +192,16 @@ lib = _load()
 def check(rc: int) -> None:
     if rc != NTX_OK:
         raise NtxError(rc, lib.ntx_last_error().decode("utf-8", "replace"))
+
+
+def copy_device_async(dst: int, src: int, n_bytes: int, stream: int) -> None:
+    """hipMemcpyAsync device to device on `stream`, from the HIP runtime this library is linked with (for results the C ABI leaves in device
+    memory of its own, into a torch tensor, in the stream's order)."""
+    fn = lib.hipMemcpyAsync
+    fn.restype, fn.argtypes = C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp]
+    err = fn(dst, src, n_bytes, 3, stream)                                    # hipMemcpyDeviceToDevice
+    if err != 0:
+        raise NtxError(NTX_E_HIP, f"hipMemcpyAsync failed: hipError_t {err}")
 
 
 def f3(values) -> "C.Array":

@@ -1,7 +1,8 @@
 // ntx_backend_flex.hip -- the layer-by-layer backend of a training step (ntx_trainer_create_flex, ntx_trainer_create_flex_ex): any Nerf /
 // ParamNerf the flex render family takes (other depths, widths, skips, color_depth; through the _ex entry also param_depth > 0) on row-major
 // activations -- flex_encode_kernel, one contraction (ntx_gemm.hip) per Dense layer and pass, the narrow heads on flex_head_*_kernel, a
-// parameter branch's output into the concatenations by flex_branch_copy_kernel.  The handle, the composite, the loss and Adam are
+// parameter branch's output into the concatenations by flex_branch_copy_kernel; where it is asked for (ntx_trainer_enable_param_gradients), dL/d params:
+// one more term per reader of the parameter features, then flex_param_fold_kernel / flex_param_rows_kernel.  The handle, the composite, the loss and Adam are
 // ntx_trainer.hip's.  gfx950 only.
 #include <algorithm>
 #include "ntx_trainer.h"
@@ -142,6 +143,59 @@ __global__ void flex_transpose_kernel(const float *__restrict__ w, float *__rest
     const int j = (int)(o / s.hid), r = (int)(o - (long long)j * s.hid);
     wt[s.dst + o] = w[s.src + (size_t)r * s.out + j];
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// dL/d params (ntx_trainer_enable_param_gradients).  The way back leaves the gradient at the parameter FEATURES of every sample,
+// PG_geo[M][ld_geo] / PG_app[M][ld_app] in the rows of FourierFeatures(parameters); the fold takes a sample's row through the encoder's
+// derivative -- the identity row plus, per band, slope(sin row) and slope(cos row) at the value x the encoder fed (blurred_param), times the
+// sample's cone_scale z for blur_idx (renderer.py:155-158) -- and adds the samples of a ray: a wave per ray, lane l the samples l, l + 64, ...
+// in ascending order, then the lanes' butterfly.  A wave's 64 samples are 64 consecutive rows of PG, one contiguous range: every line it
+// fetches is used whole over the loop along the row.  A sample of a ray that misses (z not finite) is SELECTED to 0, never multiplied:
+// its cone_scale may be NaN.  flex_param_rows_kernel then adds the rays of a parameter row in ascending ray order: neither sum depends on the
+// grid or on the trainer's capacity.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct FlexFoldArgs { StepRays r; const float *pg_geo, *pg_app; int ld_geo, ld_app; float *ray_pg; };      // ray_pg [n_rays][P], geometry columns first
+__global__ __launch_bounds__(256) void flex_param_fold_kernel(FlexFoldArgs args) {
+    const StepRays &a = args.r;
+    const int lane = threadIdx.x & 63, P = a.n_geo + a.n_app;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= a.n_rays) return;
+    const RayCtx rc = ray_ctx(a.rays_d, a.params, a.rays_per_param_row, ray, P);
+    const float *zray = a.z + (size_t)ray * a.S;
+    for (int c = 0; c < P; ++c) {
+        const bool geo = c < a.n_geo;
+        const int D = geo ? a.n_geo : a.n_app, cc = geo ? c : c - a.n_geo, ld = geo ? args.ld_geo : args.ld_app;
+        const float *pg = (geo ? args.pg_geo : args.pg_app) + (size_t)ray * a.S * ld;
+        float acc = 0.0f;
+        for (int s = lane; s < a.S; s += 64) {
+            bool hit;
+            const float z = depth_of(zray[s], hit);
+            const float x = blurred_param(rc.pr, c, a.blur_idx, hit, a.cone, ray, z);
+            const float *row = pg + (size_t)s * ld;
+            float v = row[cc];
+            for (int f = 0; f < a.param_freq; ++f) {
+                v = fmaf(fourier_slope(x, f, 0), row[fourier_row_of(D, f, 0, cc)], v);
+                v = fmaf(fourier_slope(x, f, 1), row[fourier_row_of(D, f, 1, cc)], v);
+            }
+            if (c == a.blur_idx && hit) v *= a.cone[ray] * z;
+            acc += hit ? v : 0.0f;
+        }
+        acc = wave_sumf(acc);
+        if (lane == 0) args.ray_pg[(size_t)ray * P + c] = acc;
+    }
+}
+// param_grad[row][c] = the sum of ray_pg[r][c] over the row's rays r = row * rays_per_param_row ..., ascending (the last row may be short)
+__global__ __launch_bounds__(256) void flex_param_rows_kernel(const float *__restrict__ ray_pg, long long n_rays, long long rays_per_param_row, int P, long long rows,
+                                                              float *__restrict__ out) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * P) return;
+    const long long row = e / P, r0 = row * rays_per_param_row, r1 = r0 + rays_per_param_row < n_rays ? r0 + rays_per_param_row : n_rays;
+    const int c = (int)(e - row * P);
+    float sum = 0.0f;
+#pragma unroll 8
+    for (long long r = r0; r < r1; ++r) sum += ray_pg[(size_t)r * P + c];
+    out[e] = sum;
+}
 }   // namespace ntx_train
 namespace {
 using namespace ntx_train;
@@ -156,6 +210,7 @@ struct FlexLayer {
     float *Y = nullptr; int ldy = 0;
     long long wt = -1;                                  // its transposed hidden rows [out][in - enc] in FlexBackend::wt
     long long bwt = -1;                                 // a consumer of a parameter branch: its transposed branch rows [out][param_width] in FlexBackend::wt
+    long long pwt = -1;                                 // parameter gradients on: a reader of parameter features, its transposed feature rows [out][n_in]; a branch's layer 0, its kernel whole
 };
 // A parameter branch (model.py:88-93 geometry, 96-101 appearance): param_depth Dense(param_width, relu) layers on FF(parameters), per sample
 // (with blur_idx on one of its parameters the input differs from sample to sample).  Layer j's X is the input buffer / layer j - 1's Y; every Y
@@ -180,6 +235,9 @@ struct FlexBackend : Backend {
     float *G[2] = {nullptr, nullptr};                   // the gradient at a layer's output, ping-pong
     float *BG[2] = {nullptr, nullptr};                  // ... at a branch layer's output [M][ldb] (param_width may be larger than width)
     float *wt = nullptr; FlexTSeg *tseg = nullptr; int n_tseg = 0; long long t_total = 0;
+    std::vector<FlexTSeg> segs;                         // the table on the host: enable_param_gradients appends to it
+    float *PG[2] = {nullptr, nullptr}; int ldpg[2] = {0, 0}, pg_met[2] = {0, 0};      // the gradient at the geometry / appearance parameter features [M][pad4(n_in)]; readers met on this way back
+    float *ray_pg = nullptr;                            // [cap_rays][P]: a ray's samples folded and added
     float *partial = nullptr, *colsum = nullptr;        // [n_split][in * out], [n_split][out] of the layer whose weight gradient is being taken
     FlexDst pos_dst[FLEX_MAX_DST]; int n_pos_dst = 0; FlexDst dir_dst{};
     size_t plan(const ntx_model_desc *d, int param_depth, int param_width);
@@ -187,6 +245,9 @@ struct FlexBackend : Backend {
     void branch_forward(const FlexBranch &b, const FlexDst *dst, int n_dst, long long M, hipStream_t st);
     void branch_term(FlexBranch &b, const FlexLayer &consumer, const float *dY, long long M, hipStream_t st);
     void branch_backward(const FlexBranch &b, long long M, int n_split, hipStream_t st);
+    void param_term(int group, long long pwt, int n_in, const float *dY, int lddy, int K, long long M, hipStream_t st);
+    void seg(long long &slot, size_t src, int rows, int out);
+    int enable_param_gradients() override;
     void reduce(hipStream_t st, int n_split, const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out);
     int forward(const StepRays &r, hipStream_t st) override;
     int backward(const StepRays &r, hipStream_t st) override;
@@ -264,7 +325,6 @@ void FlexBackend::place() {
     if (geo.exists() || app.exists()) { mem.alloc(&BG[0], (size_t)M * ldb); mem.alloc(&BG[1], (size_t)M * ldb); }
     const size_t splits = (size_t)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
     mem.alloc(&partial, splits * most_dw); mem.alloc(&colsum, splits * 256);
-    std::vector<FlexTSeg> segs;
     long long at = 0;
     for (size_t i = 1; i < layers.size(); ++i) {
         FlexLayer &l = layers[i];
@@ -273,13 +333,9 @@ void FlexBackend::place() {
         segs.push_back(FlexTSeg{(long long)(l.w + (size_t)l.enc * l.out), at, at, (long long)hid * l.out, hid, l.out});
         at += ((long long)hid * l.out + 3) / 4 * 4;
     }
+    t_total = at;
     // ... and the branch rows of the kernels that read a branch's output (behind the FF(xyz) rows of the map), the kernels of the branches'
     // own hidden layers whole
-    auto seg = [&](long long &slot, size_t src, int rows, int out) {
-        slot = at;
-        segs.push_back(FlexTSeg{(long long)src, at, at, (long long)rows * out, rows, out});
-        at += ((long long)rows * out + 3) / 4 * 4;
-    };
     for (size_t i = 0; i < layers.size(); ++i) {
         FlexLayer &l = layers[i];
         const bool pos_in = (int)i < d.depth && l.enc > 0, dir_in = (int)i == d.depth + 1;     // layers that read pos_map / dir_map
@@ -288,9 +344,46 @@ void FlexBackend::place() {
     }
     for (FlexBranch *b : {&geo, &app})
         for (size_t j = 1; j < b->layers.size(); ++j) seg(b->layers[j].wt, b->layers[j].w, b->layers[j].in, b->layers[j].out);
-    t_total = at; n_tseg = (int)segs.size();
-    mem.alloc(&wt, (size_t)at);
+    n_tseg = (int)segs.size();
+    mem.alloc(&wt, (size_t)t_total);
     mem.upload(&tseg, segs, "segment");
+}
+// one more segment behind the table's last: rows [src / out ...) of a kernel [.][out], transposed to [out][rows]
+void FlexBackend::seg(long long &slot, size_t src, int rows, int out) {
+    slot = t_total;
+    segs.push_back(FlexTSeg{(long long)src, t_total, t_total, (long long)rows * out, rows, out});
+    t_total += ((long long)rows * out + 3) / 4 * 4;
+}
+// What dL/d params needs, placed at the first enable for the trainer's capacity: the feature gradients, a ray's and a row's sums, and the
+// transposed parameter-feature rows of every reader (without branches: trunk layer 0 and the layers behind a skip read the geometry
+// features, the first layer that reads dir_map the appearance features; with branches: the branch's layer 0 reads them) as NEW segments
+// behind the table's last, so the places of the others in wt -- and a handle that never enables this -- stay as they are
+int FlexBackend::enable_param_gradients() {
+    if (t->P == 0) return ntx_set_error(NTX_E_INVALID, "parameter gradients: the model has no parameters (a Nerf, n_parameters [0, 0]); the layer-by-layer trainer of a "
+                                        "ParamNerf takes them (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
+    if (ray_pg) return NTX_OK;
+    DeviceMemory &mem = t->mem;
+    const ntx_model_desc &d = t->desc;
+    TRAIN_TRY(hipSetDevice(t->device));
+    FlexBranch *br[2] = {&geo, &app};
+    for (int k = 0; k < 2; ++k) {
+        if (br[k]->n_in == 0) continue;
+        ldpg[k] = pad4(br[k]->n_in);
+        mem.alloc(&PG[k], (size_t)t->cap * ldpg[k]);
+        if (br[k]->exists()) { FlexLayer &l = br[k]->layers[0]; seg(l.pwt, l.w, l.in, l.out); continue; }
+        for (size_t i = 0; i < layers.size(); ++i) {
+            FlexLayer &l = layers[i];
+            const bool reads = k == 0 ? (int)i < d.depth && l.enc > 0 : (int)i == d.depth + 1;
+            if (reads) seg(l.pwt, l.w + (size_t)br[k]->off * l.out, br[k]->n_in, l.out);
+        }
+    }
+    mem.alloc(&ray_pg, (size_t)t->cap_rays * t->P); mem.alloc(&t->param_grad, (size_t)t->cap_rays * t->P);
+    float *old_wt = wt; FlexTSeg *old_seg = tseg;
+    n_tseg = (int)segs.size();
+    mem.alloc(&wt, (size_t)t_total);                                         // (every forward pass fills it again)
+    mem.upload(&tseg, segs, "segment");
+    if (mem.rc == NTX_OK) { mem.release(old_wt); mem.release(old_seg); }
+    return mem.rc;
 }
 
 // a branch's layers, then its last output into the concatenations that hold the map
@@ -349,6 +442,13 @@ void FlexBackend::branch_term(FlexBranch &b, const FlexLayer &consumer, const fl
     g.accumulate = b.consumers_met++ > 0; g.mask = last.Y; g.ldmask = last.ldy;
     launch_gemm(st, true, g);
 }
+// A reader's term of the gradient at a group's parameter features (0 geometry, 1 appearance): PG (+)= dY . W[feature rows]^T, the readers in
+// the order the way back meets them
+void FlexBackend::param_term(int group, long long pwt, int n_in, const float *dY, int lddy, int K, long long M, hipStream_t st) {
+    GemmArgs g{}; g.A = dY; g.lda = lddy; g.B = wt + pwt; g.ldb = n_in; g.C = PG[group]; g.ldc = ldpg[group]; g.M = (int)M; g.N = n_in; g.K = K;
+    g.accumulate = pg_met[group]++ > 0;
+    launch_gemm(st, true, g);
+}
 // ... and from there through the branch, as through the trunk: dW / db per layer over ranges of FLEX_SPLIT samples, dX masked by the layer in
 // front; nothing behind the first layer (the inputs are not trained)
 void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split, hipStream_t st) {
@@ -356,11 +456,16 @@ void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split,
     for (int j = (int)b.layers.size() - 1; j >= 0; --j) {
         const FlexLayer &l = b.layers[j];
         const float *dY = BG[cur];
-        GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldb; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
-        g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
-        launch_gemm(st, false, g, n_split);
-        reduce(st, n_split, partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
-        if (j == 0) break;
+        if (t->pg_mode != 2) {
+            GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldb; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
+            g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
+            launch_gemm(st, false, g, n_split);
+            reduce(st, n_split, partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
+        }
+        if (j == 0) {                                                        // behind the first layer lie the parameter features: dY_0 . W_0^T where dL/d params is asked for
+            if (t->pg_mode != 0) param_term(&b == &geo ? 0 : 1, l.pwt, l.in, dY, ldb, l.out, M, st);
+            break;
+        }
         const FlexLayer &s = b.layers[j - 1];
         GemmArgs x{}; x.A = dY; x.lda = ldb; x.B = wt + l.wt; x.ldb = l.in; x.C = BG[cur ^ 1]; x.ldc = ldb; x.M = (int)M; x.N = l.in; x.K = l.out;
         x.mask = s.Y; x.ldmask = s.ldy;
@@ -376,19 +481,22 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
     auto reduce = [&](const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
         this->reduce(st, n_split, part, count, out, bias_partial, bias_count, bias_out);
     };
-    geo.consumers_met = app.consumers_met = 0;
+    geo.consumers_met = app.consumers_met = 0; pg_met[0] = pg_met[1] = 0;
+    const bool wgrad = t->pg_mode != 2, pgrad = t->pg_mode != 0;               // mode 2: dL/d params alone, no weight gradient is taken or reduced
     const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
     const unsigned ew = 256;
     // the colour head (model.py:123): kernel and bias lie side by side in the blob, as in a range's partial sums
     auto pow2 = [](int k) { int p = 64; while (p < k) p *= 2; return p; };
-    hipLaunchKernelGGL(flex_head_wgrad_kernel<3>, dim3((unsigned)n_split), dim3(1024), 0, st, lh.Y, lh.ldy, lh.out, pow2(lh.out), t->dgrad, 0, M, partial);
-    reduce(partial, (long long)lh.out * 3 + 3, rgb.w, nullptr, 0, 0);
+    if (wgrad) {
+        hipLaunchKernelGGL(flex_head_wgrad_kernel<3>, dim3((unsigned)n_split), dim3(1024), 0, st, lh.Y, lh.ldy, lh.out, pow2(lh.out), t->dgrad, 0, M, partial);
+        reduce(partial, (long long)lh.out * 3 + 3, rgb.w, nullptr, 0, 0);
+    }
     int cur = 0;
     hipLaunchKernelGGL(flex_head_dx_kernel<3>, dim3((unsigned)((M * lh.out + ew - 1) / ew)), dim3(ew), 0, st, t->dgrad, 0, W + rgb.w, lh.out, lh.Y, lh.ldy, G[cur], ldg, M);
     for (int i = (int)layers.size() - 1; i >= 0; --i) {
         const FlexLayer &l = layers[i];
         const float *dY = G[cur];
-        {   // dW_i and db_i
+        if (wgrad) {   // dW_i and db_i
             GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldg; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
             g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
             launch_gemm(st, false, g, n_split);
@@ -399,14 +507,19 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
             FlexBranch &b = trunk ? geo : app;
             branch_term(b, l, dY, M, st);
             if (!trunk || i == 0) branch_backward(b, M, n_split, st);        // the appearance branch has one reader; trunk layer 0 is the geometry branch's last
+        } else if (pgrad && l.pwt >= 0) {                                    // a reader of parameter features: its term, in the same order
+            const int group = i <= last_trunk ? 0 : 1;
+            param_term(group, l.pwt, (group == 0 ? geo : app).n_in, dY, ldg, l.out, M, st);
         }
-        if (i == 0) break;                                                   // the inputs are not trained
+        if (i == 0) break;                                                   // positions and directions take no gradient
         const FlexLayer &s = layers[l.src];
         float *dX = G[cur ^ 1];
         int accumulate = 0;
         if (l.src == last_trunk) {                                           // the density head hangs on the same output (model.py:111): its rank-1 term first
-            hipLaunchKernelGGL(flex_head_wgrad_kernel<1>, dim3((unsigned)n_split), dim3(1024), 0, st, lt.Y, lt.ldy, lt.out, pow2(lt.out), t->dgrad, 3, M, partial);
-            reduce(partial, (long long)lt.out + 1, alpha.w, nullptr, 0, 0);
+            if (wgrad) {
+                hipLaunchKernelGGL(flex_head_wgrad_kernel<1>, dim3((unsigned)n_split), dim3(1024), 0, st, lt.Y, lt.ldy, lt.out, pow2(lt.out), t->dgrad, 3, M, partial);
+                reduce(partial, (long long)lt.out + 1, alpha.w, nullptr, 0, 0);
+            }
             hipLaunchKernelGGL(flex_head_dx_kernel<1>, dim3((unsigned)((M * lt.out + ew - 1) / ew)), dim3(ew), 0, st, t->dgrad, 3, W + alpha.w, lt.out, (const float *)nullptr, 0, dX,
                                ldg, M);
             accumulate = 1;
@@ -416,6 +529,13 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
         if (s.relu) { g.mask = s.Y; g.ldmask = s.ldy; }
         launch_gemm(st, true, g);
         cur ^= 1;
+    }
+    if (pgrad) {                                                             // the features' gradient through the encoder, a ray's samples, a row's rays
+        const int P = t->P;
+        const long long rows = (r.n_rays + r.rays_per_param_row - 1) / r.rays_per_param_row;
+        FlexFoldArgs f{}; f.r = r; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.ray_pg = ray_pg;
+        hipLaunchKernelGGL(flex_param_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
+        hipLaunchKernelGGL(flex_param_rows_kernel, dim3((unsigned)((rows * P + 255) / 256)), dim3(256), 0, st, ray_pg, r.n_rays, r.rays_per_param_row, P, rows, t->param_grad);
     }
     return NTX_OK;
 }

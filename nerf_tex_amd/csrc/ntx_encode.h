@@ -38,6 +38,12 @@ __device__ __forceinline__ float spliced_param(const float *pr, int k, int splic
 // FourierFeatures(x[0 .. D), L) = [x | sin(2^0 x) | cos(2^0 x) | sin(2^1 x) | ...], every block D wide: the value of (band, h = 0 sin / 1 cos),
 // the row it lands on, and row r as a function of r
 __device__ __forceinline__ float fourier_value(float x, int band, int h) { return ntx::sin_q(ldexpf(1.0f, band) * x, h); }
+// ... and its slope d/dx: 2^band cos(2^band x) for the sine row, -2^band sin(2^band x) for the cosine row -- on the same sin_q the value
+// came from (the way back from the parameter features to the parameters: ntx_trainer_enable_param_gradients)
+__device__ __forceinline__ float fourier_slope(float x, int band, int h) {
+    const float w = ldexpf(1.0f, band), s = ntx::sin_q(w * x, 1 - h);
+    return h ? -(w * s) : w * s;
+}
 __device__ __forceinline__ int fourier_row_of(int D, int band, int h, int c) { return D + 2 * D * band + h * D + c; }
 template <class X>
 __device__ __forceinline__ float fourier_row(int r, int D, X x) {

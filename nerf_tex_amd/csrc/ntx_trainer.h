@@ -34,6 +34,9 @@ struct DeviceMemory {
             rc = ntx_set_error(NTX_E_HIP, "%s table upload failed", what);
         return rc;
     }
+    void release(void *p) {                                                  // one allocation given back early (hipFree waits for what is in flight)
+        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { (void)hipFree(p); ptrs.erase(ptrs.begin() + i); return; }
+    }
     ~DeviceMemory() { for (void *p : ptrs) (void)hipFree(p); }
 };
 
@@ -50,6 +53,11 @@ struct Backend {
     virtual int forward(const StepRays &r, hipStream_t st) = 0;
     virtual int backward(const StepRays &r, hipStream_t st) = 0;
     virtual int activation(int layer, int64_t n_samples_total, float *out_host) = 0;   // ntx_trainer_activation, the arguments checked
+    // ntx_trainer_enable_param_gradients, mode 1 / 2 on a model with parameters: places what dL/d params needs (once); the handle keeps the mode
+    virtual int enable_param_gradients() {
+        return ntx_set_error(NTX_E_UNSUPPORTED, "parameter gradients: the fused chain (ntx_trainer_create) stops at the encoded inputs; the layer-by-layer "
+                             "trainer takes the same model (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
+    }
 };
 // what an entry's architecture check makes of a descriptor
 struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; int param_depth, param_width; };   // param_*: the branches the model HAS (0 without parameters)
@@ -69,6 +77,9 @@ struct ntx_trainer {
     float *dgrad = nullptr, *dhead = nullptr;  // the composite's adjoint [M][4], and the same as one O-layout tile per block (the chain's narrow heads' dY)
     float *color = nullptr, *alpha_out = nullptr, *ray_loss = nullptr, *loss = nullptr;
     float *weights_out = nullptr;              // caller's [N][S] buffer for the composite's weights of the next steps, or NULL
+    int pg_mode = 0;                           // ntx_trainer_enable_param_gradients: 0 off, 1 dL/d params beside the weight gradients, 2 dL/d params alone
+    float *param_grad = nullptr;               // [rows][P] of the last step (the backend places it at the first enable), pg_rows = 0: no step yet
+    long long pg_rows = 0;
     long long adam_iterations = 0;
     ntx_train::Backend *backend = nullptr;
     ntx_train::DeviceMemory mem;               // (destroyed after the body below has run)

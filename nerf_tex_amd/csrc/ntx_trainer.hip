@@ -290,8 +290,15 @@ __global__ void add_kernel(float *__restrict__ dst, const float *__restrict__ sr
 }
 }   // namespace ntx_train
 
+// mode 2 of ntx_trainer_enable_param_gradients takes no weight gradient: what would use one says so
+static int no_weight_gradients(const ntx_trainer *t, const char *who) {
+    return t->pg_mode == 2 ? ntx_set_error(NTX_E_INVALID, "%s: the trainer takes parameter gradients only (ntx_trainer_enable_param_gradients mode 2), its weight gradient is "
+                                           "not this step's; set mode 0 or 1 first", who) : NTX_OK;
+}
+
 int ntx_trainer_stash_gradients(ntx_trainer *t, int op, ntx_stream stream) {
     if (!t || (op != 0 && op != 1)) return ntx_set_error(NTX_E_INVALID, "trainer is NULL or op is not 0 (keep) / 1 (add back)");
+    if (int rc = no_weight_gradients(t, "ntx_trainer_stash_gradients")) return rc;
     TRAIN_TRY(hipSetDevice(t->device));
     if (!t->stash) {
         if (op == 1) return ntx_set_error(NTX_E_INVALID, "no gradient was kept");
@@ -311,6 +318,7 @@ int ntx_trainer_device_weights(ntx_trainer *t, const float **weights_dev) {
 
 int ntx_trainer_allreduce_gradients(ntx_trainer *t, ntx_comm *comm, ntx_stream stream) {
     if (!t || !comm) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (int rc = no_weight_gradients(t, "ntx_trainer_allreduce_gradients")) return rc;
     return ntx_allreduce_mean_f32(comm, t->grad, t->n_weights, stream);
 }
 
@@ -363,11 +371,31 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
     rc = t->backend->backward(rays, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
+    if (t->pg_mode != 0) t->pg_rows = (n_rays + rays_per_param_row - 1) / rays_per_param_row;
+    return NTX_OK;
+}
+
+int ntx_trainer_enable_param_gradients(ntx_trainer *t, int mode) {
+    if (!t || mode < 0 || mode > 2) return ntx_set_error(NTX_E_INVALID, "trainer is NULL or mode is not 0 (off) / 1 (with the weight gradients) / 2 (parameters only)");
+    if (mode != 0) {
+        int rc = t->backend->enable_param_gradients();                                          // the chain refuses; the layer-by-layer backend places its buffers once
+        if (rc != NTX_OK) return rc;
+    } else t->pg_rows = 0;
+    t->pg_mode = mode;
+    return NTX_OK;
+}
+
+int ntx_trainer_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *rows, int *n_params) {
+    if (!t || !grad_dev || !rows || !n_params) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (t->pg_mode == 0 || t->pg_rows == 0) return ntx_set_error(NTX_E_INVALID, "no parameter gradients: %s", t->pg_mode == 0 ? "ntx_trainer_enable_param_gradients is off" :
+                                                                 "no step has run since they were enabled");
+    *grad_dev = t->param_grad; *rows = t->pg_rows; *n_params = t->P;
     return NTX_OK;
 }
 
 int ntx_trainer_adam_step(ntx_trainer *t, float lrate, float lrate_decay_steps, float lrate_decay_rate, float beta_1, float beta_2, float epsilon, ntx_stream stream) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    if (int rc = no_weight_gradients(t, "ntx_trainer_adam_step")) return rc;
     TRAIN_TRY(hipSetDevice(t->device));
     const double step = (double)t->adam_iterations;
     double lr = lrate;

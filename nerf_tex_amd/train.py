@@ -16,7 +16,9 @@ it), with FourierFeatures under the Renderer or -- an IntegratedPositionalEncodi
 takes (FourierFeatures; depth 1..24, width 2..256, color_depth 0..4, skips below depth-1, no parameter branches) layer by layer: one
 contraction per Dense layer and pass (`ntx_trainer_create_flex`); `BranchTrainer` is the same step for a ParamNerf with parameter branches
 (param_depth 1..4, param_width 2..128: `ntx_trainer_create_flex_ex`).  `trainer_for(model, ...)` picks between them, and
-`Trainer.from_config`, `CoarseFineTrainer` and `Train` build their trainers through it."""
+`Trainer.from_config`, `CoarseFineTrainer` and `Train` build their trainers through it.  The layer-by-layer trainers also take the one
+gradient a training step otherwise leaves out, dL/d material parameters (`param_gradients=`, `parameter_gradients()`); `nerf_tex_amd.fit`
+fits parameters to target images with it."""
 
 from __future__ import annotations
 
@@ -300,6 +302,40 @@ class FlexTrainer(Trainer):
     _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create_flex(*a))
     _widen = staticmethod(lambda model: None)                                      # every width trains as it is
 
+    def __init__(self, model, *args, param_gradients=False, **kw) -> None:
+        """`Trainer`'s arguments, and `param_gradients`: False, True -- every `gradients_step` also leaves dL/d parameters
+        (`parameter_gradients()`), the weight gradients bit for bit as without it -- or "only": the same parameter gradients and no weight
+        gradient at all (`gradients()` keeps what it held; `apply_gradients` raises NTX_E_INVALID).  For a model with parameters
+        (`ntx_trainer_enable_param_gradients`)."""
+        super().__init__(model, *args, **kw)
+        self.param_gradients = False
+        if param_gradients is not False:
+            self.set_param_gradients(param_gradients)
+
+    def set_param_gradients(self, mode) -> None:
+        """False / True / "only" for the following steps (the buffers are placed at the first True or "only")."""
+        modes = {False: 0, True: 1, "only": 2}
+        if isinstance(mode, (int, str)) and mode in modes:
+            native = modes[mode]
+        else:
+            raise ValueError(f'param_gradients must be False, True or "only", not {mode!r}')
+        import torch
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.ntx_trainer_enable_param_gradients(self._h, native))
+        self.param_gradients = "only" if native == 2 else bool(native)
+
+    def parameter_gradients(self):
+        """dL/d parameters of the last step: a torch tensor [rows, P] on the trainer's device (rows = the step's parameter rows,
+        ceil(n_rays / rays_per_param_row); geometry columns first), a copy in the current stream's order."""
+        import torch
+        ptr, rows, n = C.c_void_p(), C.c_int64(), C.c_int()
+        _lib.check(_lib.lib.ntx_trainer_param_gradients(self._h, C.byref(ptr), C.byref(rows), C.byref(n)))
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((int(rows.value), int(n.value)), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
     def relu_widths(self):
         """Widths of the ReLU layers in the order of `activation`'s indices (and of the oracle's masks): trunk, colour layers, colour half."""
         m = self.model
@@ -361,13 +397,14 @@ def _chain_takes(model) -> bool:
     return _widened(model) is not None and model.n_pos == 3
 
 
-def trainer_class_for(model, branches: bool = False):
+def trainer_class_for(model, branches: bool = False, param_gradients=False):
     """The class that trains `model`, without creating anything (no device is asked for): `Trainer` where the fused chain takes it,
     `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise -- which is what a
     model with parameter branches gets unless `branches` is set: then a model with param_depth > 0 and at least one parameter gets
-    `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it."""
+    `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it.  `param_gradients` (True or "only"): the layer-by-layer class also where
+    the chain would take the model -- the chain stops at the encoded inputs."""
     import numpy as np
-    if _chain_takes(model):
+    if _chain_takes(model) and param_gradients is False:
         return Trainer
     cls = BranchTrainer if branches and model.param_depth > 0 and model.n_params > 0 else FlexTrainer
     desc, h = model.desc(), C.c_void_p()
@@ -380,8 +417,12 @@ def trainer_class_for(model, branches: bool = False):
 
 
 def trainer_for(model, **kw):
-    """`Trainer(model, **kw)`, `FlexTrainer(model, **kw)` or `BranchTrainer(model, **kw)`, whichever `trainer_class_for(model, branches=True)` names."""
-    return trainer_class_for(model, branches=True)(model, **kw)
+    """`Trainer(model, **kw)`, `FlexTrainer(model, **kw)` or `BranchTrainer(model, **kw)`, whichever `trainer_class_for(model, branches=True)`
+    names; with `param_gradients=True` / "only" the layer-by-layer class in any case (it is the one that takes them)."""
+    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False))
+    if cls is Trainer:
+        kw.pop("param_gradients", None)                                        # (False: the chain has no such argument)
+    return cls(model, **kw)
 
 
 class CoarseFineTrainer:
