@@ -52,6 +52,8 @@ class ParameterFitter:
         params = torch.as_tensor(init, dtype=torch.float32).to(dev).clone().contiguous()
         if params.dim() != 2:
             raise ValueError("init must be [B, P]: one parameter row per image")
+        if params.shape[1] != self.model.n_params:
+            raise ValueError(f"init has {params.shape[1]} columns, the model takes {self.model.n_params} parameters")
         params.requires_grad_(True)
         params.grad = torch.zeros_like(params)
         opt = torch.optim.Adam([params], lr=self.lrate)

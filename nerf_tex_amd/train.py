@@ -215,6 +215,12 @@ class Trainer:
         to = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32).contiguous()
         rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, z_vals = (to(a) for a in (rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, z_vals))
         n = rays_o.reshape(-1, 3).shape[0]
+        P_in = int(getattr(self.model, "n_params", 0)) + (1 if self.mip else 0)
+        if P_in > 0 and parameters is not None:                                # the kernels read row ray // rays_per_param_row of it unasked: a count of floats, no shape test
+            need = -(-n // max(1, int(rays_per_param_row))) * P_in
+            if parameters.numel() < need:
+                raise ValueError(f"parameters holds {parameters.numel()} floats, the step reads {need}: ceil({n} rays / {max(1, int(rays_per_param_row))} rays a row) rows "
+                                 f"of {P_in}")
         self._last_rays = n
         flags = (_lib.FLAG_PERTURB if self.perturb else 0) | (_lib.FLAG_MAP_EXR if self.map_exr else 0) | (_lib.FLAG_COMPOSITE_BKGD if composite_bkgd else 0)
         opts = None

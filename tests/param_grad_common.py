@@ -86,46 +86,108 @@ OPTION_CASES = [
 ]
 MISS_RAYS = [0, 5, 33, 34] + list(range(35, 70))                                                        # with 35 rays a row: the whole last row
 MISS_CASE = ("rays_that_miss", *SMALL, dict(rpr=35, miss=MISS_RAYS, perturb=True), (11, 3))
-ALL_CASES = MODEL_CASES + ROW_CASES + OPTION_CASES + [MISS_CASE]
-DEFAULTS = dict(loss_name="alpha_smape", bkgd=False, map_exr=False, perturb=False, blur=None, noise_std=0.0, rpr=35, miss=())
+DEFAULTS = dict(loss_name="alpha_smape", bkgd=False, map_exr=False, perturb=False, blur=None, noise_std=0.0, rpr=35, miss=(), miss_cone="nan", n=N_RAYS, S=N_SAMPLES,
+                z=None, NI=27)
+
+# ---- the edges (profiles/param_gradients/edge_errors.md).  A case's knobs carry its own size (`n` rays x `S` samples) and, with z="merged", its
+# own depths.  Every one of these sits 2x inside both guards of `fair` on the CPU (floor <= 2.5e-4, max |grad| >= 2e-6), so that the trainer's own
+# ReLU patterns cannot tip a guard on the GPU.
+# The fold's trips along a ray: lane l takes the samples l, l + 64, ...: every lane once (64), one lane twice (65), a third trip (129), the configs'
+# 256 (9 x 256 = 2304 samples: across one range of the weight gradients), fewer samples than lanes, the step's minimum (batch seed 3 is unfair at
+# S = 2: floor 1.3e-3)
+SAMPLE_CASES = [(f"samples_{n}x{S}", *SMALL, dict(n=n, S=S, rpr=r), (11, bs)) for n, S, r, bs in ((6, 64, 3, 3), (6, 65, 3, 3), (6, 129, 3, 3), (9, 256, 4, 3), (5, 3, 2, 3),
+                                                                                                  (10, 2, 5, 5))]
+# The rows' loop over a row's rays is unrolled by 8: rows of 7 / 8 / 9 rays (the last one short: 6, 4, 2), a row longer than the batch, one ray
+# in all, a whole row and a row of one
+ROW_EDGE_CASES = [(f"rows_{n}_by_{r}", *SMALL, dict(n=n, rpr=r), (11, 3)) for n, r in ((20, 7), (20, 8), (20, 9), (20, 32), (1, 1), (3, 2))]
+# The built limits -- n_parameters [4, 8] with 4 bands: 36 and 72 feature columns, P = 12, blur_idx on the first and last column of each group --,
+# one-group models without branches (PG[0] or PG[1] is never placed), and branches whose input rows differ from sample to sample (blur_idx)
+_TRUNK, _EDGE = dict(width=64, depth=3, skips=[1]), dict(n=20, rpr=10)
+LIMIT_CASES = ([(f"limit_4_8_blur_{b}", (4, 8), _TRUNK, None, "carpet", dict(_EDGE, blur=b), (11, 3)) for b in (None, 0, 3, 4, 11)]
+               + [(f"one_group_{g}_{a}", (g, a), _TRUNK, None, "carpet", dict(_EDGE), (11, 3)) for g, a in ((0, 3), (2, 0), (1, 0), (0, 1))]
+               + [(f"branches_blur_{b}", (2, 3), dict(_TRUNK, param_depth=2, param_width=16), None, "grass_filtered", dict(_EDGE, blur=b), (11, 3)) for b in (0, 3)])
+# Missed rays under blur_idx: the fold reads cone_scale, which is NaN for every other missed ray and +inf for the rest
+MISS_BLUR_CASES = [(f"miss_blur_{b}", (2, 3), _TRUNK, None, "grass_filtered", dict(rpr=35, miss=MISS_RAYS, miss_cone="nan_inf", perturb=True, blur=b), (11, 3)) for b in (0, 3)]
+# Caller's depths (the fine pass of coarse + fine): non-uniform, and a factor of the blurred column
+DEPTH_CASES = [(f"depths_blur_{b}", *SMALL, dict(n=10, S=40, NI=27, z="merged", rpr=5, blur=b), (11, 3)) for b in (None, 0, 1, 6)]
+# The coarse pass of the coarse + fine test (its fine pass runs on the depths the trainer's sampler merges: no CPU case), and ParameterFitter's options
+COARSE_CASE = ("coarse_pass", *SMALL, dict(n=24, S=24, rpr=12, perturb=True), (11, 3))
+FITTER_CASE = ("fitter_options", *SMALL, dict(blur=0, perturb=True, noise_std=0.1, map_exr=True), (11, 3))
+NEW_CASES = SAMPLE_CASES + ROW_EDGE_CASES + LIMIT_CASES + MISS_BLUR_CASES + DEPTH_CASES + [COARSE_CASE, FITTER_CASE]
+ALL_CASES = MODEL_CASES + ROW_CASES + OPTION_CASES + [MISS_CASE] + NEW_CASES
+MARGIN = 2.0                                                                     # how far inside `fair`'s guards every case of NEW_CASES sits on the CPU
 
 
-def case_setup(case, n=N_RAYS, S=N_SAMPLES):
-    """(model, spec, weights, (ro, rd, t, cone, rows, color, alpha), knobs with every default, step seed) of a case: the batch is
-    `tests.train_flex_common.flex_batch`'s, the parameter rows the first ray's of every `rpr` rays; the rays of `miss` get t = inf and
-    cone_scale = NaN."""
+def case_setup(case, n=None, S=None):
+    """(model, spec, weights, (ro, rd, t, cone, rows, color, alpha), knobs with every default, step seed) of a case at its own size (`n`, `S`:
+    another one): the batch is `tests.train_flex_common.flex_batch`'s -- a model with more parameters than the family's batch carries draws the
+    missing columns --, the parameter rows the first ray's of every `rpr` rays; the rays of `miss` get t = inf and cone_scale = NaN (miss_cone
+    "nan_inf": NaN and +inf in turn).  The knobs come back with `n`, `S` = the samples the step runs on, `miss` as a mask and `z` = None (the
+    step places its depths) or, for z="merged", z_vals [n, S] on the host: the step's own depths merged and sorted with `NI` float32 draws
+    t0 + u (t1 - t0)."""
     from tests.common import make_model
     from tests.train_flex_common import flex_batch
     cid, npar, arch, freqs, fam, knobs, (seed, batch_seed) = case
     model, spec, wts = make_model(npar, dense_media=True, arch=arch, freqs=freqs)
     kn = dict(DEFAULTS, **knobs)
+    n, S = int(n or kn["n"]), int(S or kn["S"])
     ro, rd, t, cone, params, color, alpha = flex_batch(batch_seed, n, S, spec, fam)
+    P = sum(spec.n_parameters)
+    if params.shape[1] < P:
+        more = np.random.default_rng(batch_seed).uniform(0.2, 1.5, size=(n, P - params.shape[1])).astype(F)
+        params = np.ascontiguousarray(np.concatenate([params, more], 1))
     rows = np.ascontiguousarray(params[::kn["rpr"]], F)
     miss = np.zeros(n, bool); miss[list(kn["miss"])] = True
     t = t.copy(); t[miss] = np.inf
     cone = cone.copy(); cone[miss] = np.nan
+    if kn["miss_cone"] == "nan_inf":
+        cone[np.nonzero(miss)[0][1::2]] = np.inf
     kn["miss"] = miss
+    if kn["z"] == "merged":
+        assert not miss.any()
+        u = np.random.default_rng(batch_seed).uniform(0, 1, size=(n, kn["NI"])).astype(F)
+        drawn = t[:, :1] + u * (t[:, 1:] - t[:, :1])
+        kn["z"] = np.ascontiguousarray(np.sort(np.concatenate([step_depths(t, S, seed, kn["perturb"]), drawn], 1), 1), F)
+        S += kn["NI"]
+    else:
+        assert kn["z"] is None
+    kn["n"], kn["S"] = n, S
     return model, spec, wts, (ro, rd, t, cone, rows, color, alpha), kn, seed
 
 
-def restate(spec, wts, batch, kn, seed, S, dtype, masks, branch_masks, sigma_mask):
-    """`restated_param_gradients` of a case's step on the depths and the noise the step places itself."""
+def _depths(t, kn, seed, miss=None):
+    """The depths of a case's step: the ones it was given, or the ones it places itself."""
+    if kn["z"] is None:
+        return step_depths(t, kn["S"], seed, kn["perturb"], miss)
+    z = kn["z"].copy()
+    if miss is not None:
+        z[miss] = np.inf
+    return z
+
+
+def _cone(cone):
+    """cone_scale as the restatement takes it: a missed ray's NaN / inf (the ray is filtered out) as 0."""
+    return np.where(np.isfinite(cone), cone, 0).astype(F)
+
+
+def restate(spec, wts, batch, kn, seed, dtype, masks, branch_masks, sigma_mask):
+    """`restated_param_gradients` of a case's step on the depths and the noise the step places itself, or on the case's own depths as they are."""
     from tests.train_common import LOSSES
     ro, rd, t, cone, rows, color, alpha = batch
-    z, noise = step_depths(t, S, seed, kn["perturb"], kn["miss"]), step_noise(len(t), S, seed, kn["noise_std"])
-    return restated_param_gradients(wts, spec, ro, rd, z, rows, kn["rpr"], np.nan_to_num(cone), color, alpha, LOSSES[kn["loss_name"]][0], blur_idx=kn["blur"],
+    z, noise = _depths(t, kn, seed, kn["miss"]), step_noise(len(t), kn["S"], seed, kn["noise_std"])
+    return restated_param_gradients(wts, spec, ro, rd, z, rows, kn["rpr"], _cone(cone), color, alpha, LOSSES[kn["loss_name"]][0], blur_idx=kn["blur"],
                                     map_exr=kn["map_exr"], composite_bkgd=kn["bkgd"], bkgd=BKGD, dtype=dtype, masks=masks, branch_masks=branch_masks, sigma_mask=sigma_mask,
                                     noise=noise)
 
 
-def own_patterns(spec, wts, batch, kn, seed, S):
+def own_patterns(spec, wts, batch, kn, seed):
     """The ReLU patterns of a float32 forward pass of the restatement itself (the hit rays' real, the others' whatever: they are filtered):
     what a float32 step would hand to float64 -- the CPU's stand-in for the patterns a trainer keeps."""
     ro, rd, t, cone, rows, color, alpha = batch
     n = len(t)
-    z, noise = step_depths(t, S, seed, kn["perturb"]), step_noise(n, S, seed, kn["noise_std"])
+    z, noise = _depths(t, kn, seed), step_noise(n, kn["S"], seed, kn["noise_std"])
     per_ray = np.repeat(rows, kn["rpr"], 0)[:n]
-    return tbo.own_masks(wts, spec, ro, rd, z, per_ray, np.nan_to_num(cone), blur_idx=kn["blur"], noise=noise)
+    return tbo.own_masks(wts, spec, ro, rd, z, per_ray, _cone(cone), blur_idx=kn["blur"], noise=noise)
 
 
 def trainer_patterns(tr, spec, n, S, noise):
@@ -140,15 +202,17 @@ def trainer_patterns(tr, spec, n, S, noise):
     return masks, branch_masks, sigma_mask
 
 
-def fair(want_grad, f32_grad, report=print, rows=None):
+def fair(want_grad, f32_grad, report=print, rows=None, margin=1.0):
     """The guards that keep the floor from hiding a failure, per parameter column (over `rows`, default all): the float32 restatement within 5e-4
-    of float64, and a gradient worth the name (max |grad| > 1e-6).  Returns the floors."""
+    of float64, and a gradient worth the name (max |grad| > 1e-6).  `margin`: how many times inside both guards the case has to sit (the CPU's
+    check of the cases in NEW_CASES: MARGIN).  Returns the floors."""
     sel = slice(None) if rows is None else rows
     floors, biggest = column_errors(f32_grad[sel], want_grad[sel]), np.abs(want_grad[sel]).max(0)
     for c in range(len(floors)):
         report(f"  column {c}: floor {floors[c]:.2e} max |grad| {biggest[c]:.3e}")
     assert (biggest > 1e-6).all(), ("a parameter column without a gradient worth the name: change the seed, not the bar", biggest)
     assert (floors <= 5e-4).all(), ("a float32 floor above 5e-4: change the seed, not the bar", floors)
+    assert (biggest >= 1e-6 * margin).all() and (floors <= 5e-4 / margin).all(), (f"less than {margin}x inside a guard: change the seed, not the bar", floors, biggest)
     return floors
 
 

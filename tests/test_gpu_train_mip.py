@@ -88,7 +88,8 @@ def test_mip_step_matches_the_mip_renderer():
     row = params[:1]
     color, alpha = targets(n, 6)
     okw, loss = make_loss("alpha_smape")
-    tr = Trainer(model, max_rays=n, n_samples=S, perturb=True, blur_idx=blur, raw_noise_std=0.1)
+    # (lrate: three of Adam's first steps at the default 5e-4 close the density of this network on every ray, and an image of zeros compares nothing)
+    tr = Trainer(model, max_rays=n, n_samples=S, perturb=True, blur_idx=blur, raw_noise_std=0.1, lrate=1e-5)
     val, cp, ap = tr.gradients_step(ro, rd, t, row, cone, color, alpha, loss, seed=seed, rays_per_param_row=n)
     d = lambda x: torch.as_tensor(x, device=dev())
     view = dict(rays_o=d(ro)[None], rays_d=d(rd)[None], t=d(t)[None], parameters=d(row), cone_scale=d(cone).reshape(1, -1, 1))
@@ -102,7 +103,8 @@ def test_mip_step_matches_the_mip_renderer():
     val2, cp2, ap2 = tr.gradients_step(ro, rd, t, row, cone, color, alpha, loss, seed=seed, rays_per_param_row=n, z_vals=z)
     assert float(val2.item()) == float(val.item()) and torch.equal(cp2, cp) and torch.equal(ap2, ap) and np.array_equal(tr.gradients(), g0)
     for _ in range(3):
-        tr.step(ro, rd, t, row, cone, color, alpha, loss)
+        tr.step(ro, rd, t, row, cone, color, alpha, loss, rays_per_param_row=n)       # (one row for all rays: without it the step would read 511 rows past it)
+    assert tr.iterations == 3 and not np.array_equal(tr.weights(), np.asarray(model.get_blob(), np.float32))
     rt = MipRenderer(model=twin, n_samples=S, perturb=False, blur_idx=blur)
     twin.set_weights_from_trainer(tr)
     on_device = rt(**view, training=False)
