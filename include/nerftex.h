@@ -631,6 +631,25 @@ int ntx_trainer_enable_param_gradients(ntx_trainer *t, int mode);
  * rays_per_param_row) of that step and n_params = n_geo + n_app, geometry columns first; written in the step's stream order, valid until
  * the next step.  NTX_E_INVALID when the mode is 0 or no step has run since it was enabled. */
 int ntx_trainer_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *rows, int *n_params);
+/* A step under ANY loss (ABI v7, appended): ntx_train_step_gradients cut in two at the predictions.  Every gradient of a step is linear in
+ * dL/d color_pred and dL/d alpha_pred, so a caller that evaluates its own loss on the predictions and hands back those two cotangents gets
+ * the gradients of that loss; the network, the composite and its adjoint stay the library's kernels.
+ * ntx_train_forward: ntx_train_step_gradients' arguments, checks and meaning less the loss and the targets -- depths, noise, the network with
+ * every activation kept, the composite -- and color_pred[N,3] / alpha_pred[N] (DEVICE, each may be NULL).  The step is then PENDING in the
+ * handle.  CONTRACT: until its ntx_train_backward, the caller keeps rays_o, rays_d, params, cone_scale and z_vals alive and unchanged (the
+ * way back reads them again; depths the entry sampled itself are the handle's), runs nothing else on the handle that takes a step, and
+ * queues the backward on a stream ordered behind the forward's.
+ * ntx_train_backward: d_color[N,3] = dL/d color_pred, d_alpha[N] = dL/d alpha_pred or NULL for 0 (DEVICE) -> the composite's adjoint and the
+ * way back through the network: the weight gradients in the trainer, dL/d params under ntx_trainer_enable_param_gradients mode 1 / 2 (mode
+ * 2: no weight gradient, as in the fused step) -- with the cotangents of a loss ntx_train_step_gradients knows, bit for bit that entry's.
+ * A ray that missed the proxy (tnear_far inf) takes no gradient whatever its cotangent holds, NaN and inf included.
+ * ONE backward per forward: NTX_E_INVALID without a pending forward, on a second call, on a NULL d_color (the forward stays pending).
+ * ntx_train_step_gradients and a new ntx_train_forward drop a pending step.  A handle that never calls these entries is what it was.
+ * Out of scope: second-order gradients (nothing differentiates the backward), and a coarse + fine pair as one differentiable op. */
+int ntx_train_forward(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
+                      const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
+                      const ntx_render_opts *opts, const float *z_vals, float *color_pred, float *alpha_pred, ntx_stream stream);
+int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alpha, ntx_stream stream);
 
 #ifdef __cplusplus
 }

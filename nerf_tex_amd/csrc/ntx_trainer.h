@@ -14,7 +14,7 @@
         if (e_ != hipSuccess) return ntx_set_error(NTX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 namespace ntx_train {
-constexpr int MAX_TRAIN_SAMPLES = 1024;                // samples per ray (composite_loss_kernel holds a ray in LDS)
+constexpr int MAX_TRAIN_SAMPLES = 1024;                // samples per ray (the composite kernels hold a ray in LDS)
 // Every device allocation of a handle and its backend: what is on the list is freed with the handle, and nothing else is.  The first failure
 // sticks (rc): the allocations behind it are skipped, so a create runs through and looks at rc once.
 struct DeviceMemory {
@@ -47,7 +47,8 @@ struct StepRays {
     int n_blocks() const { return (int)((M() + 31) / 32); }       // blocks of 32 samples
 };
 // The network between the encoded rays and the composite.  forward leaves sigma, raw_rgb and dists in the handle's buffers and keeps what the
-// way back needs; backward takes the handle's dgrad (and its O-layout copy dhead) to the handle's grad.
+// way back needs; backward takes the handle's dgrad (and its O-layout copy dhead) to the handle's grad -- right behind the forward
+// (ntx_train_step_gradients) or later from the same StepRays (ntx_train_backward: the caller keeps the rays' buffers alive until then).
 struct Backend {
     virtual ~Backend() {}                                                            // (its device buffers are on the handle's list)
     virtual int forward(const StepRays &r, hipStream_t st) = 0;
@@ -81,6 +82,8 @@ struct ntx_trainer {
     float *param_grad = nullptr;               // [rows][P] of the last step (the backend places it at the first enable), pg_rows = 0: no step yet
     long long pg_rows = 0;
     long long adam_iterations = 0;
+    // ntx_train_forward's step until its ntx_train_backward: the caller's rays (alive and unchanged until then), what the composite was run with
+    struct Pending { bool open = false; ntx_train::StepRays rays{}; uint32_t flags = 0; float bkgd[3] = {1.0f, 1.0f, 1.0f}; const float *noise = nullptr; } pending;
     ntx_train::Backend *backend = nullptr;
     ntx_train::DeviceMemory mem;               // (destroyed after the body below has run)
     ~ntx_trainer() { (void)hipSetDevice(device); delete backend; }

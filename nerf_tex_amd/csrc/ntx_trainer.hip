@@ -2,7 +2,9 @@
 // network/loss.py:6-59, Adam under ExponentialDecay).  This file is what every architecture shares: the handle behind ntx_trainer_* and its
 // create, the step's skeleton (depths, noise, the backend's forward, composite + loss, the backend's backward), and the kernels around the
 // network: composite_loss_kernel (renderer.py:170-213 per ray, the ray's term of the loss and the adjoint of both), reduce_batch_kernel (the
-// weight gradients' partial sums added in a fixed order: a step is bit-reproducible), adam_kernel (train.py:49-52).
+// weight gradients' partial sums added in a fixed order: a step is bit-reproducible), adam_kernel (train.py:49-52).  The same step cut in
+// two at the predictions, for a loss the caller evaluates (ntx_train_forward / ntx_train_backward): composite_forward_kernel and
+// composite_adjoint_kernel, made of the device pieces composite_loss_kernel is made of.
 // The network between the encoded rays and the composite is a backend's (ntx_trainer.h): the 8 x 256 chain of ntx_backend_chain.hip behind
 // ntx_trainer_create, the layer-by-layer step of ntx_backend_flex.hip behind ntx_trainer_create_flex / _flex_ex.  Inference fuses the whole network into
 // one kernel because nothing of it has to survive (ntx_device.h); a training step has to keep every layer's activations for the weight
@@ -66,23 +68,20 @@ __device__ __forceinline__ void loss_term(int fn, float t, float p, float inv_n,
     }
 }
 __device__ __forceinline__ size_t dhead_at(long long m, int row) { return o_index(m >> 5, 1, row, (int)(m & 31)); }
-__global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
-    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (blockIdx.x == 0) {                                 // the tail of the last block of 32 samples: no gradient
-        const long long end = (a.M + 31) / 32 * 32;
-        for (long long m = a.M + threadIdx.x; m < end; m += 256)
-            for (int r = 0; r < 4; ++r) a.dhead[dhead_at(m, r)] = 0.0f;
-    }
-    const int ray = blockIdx.x * 4 + wave;
-    if (ray >= a.n_rays) return;
+// the tail of the last block of 32 samples: no gradient (the threads of one workgroup)
+__device__ __forceinline__ void zero_dhead_tail(const CompositeArgs &a) {
+    const long long end = (a.M + 31) / 32 * 32;
+    for (long long m = a.M + threadIdx.x; m < end; m += 256)
+        for (int r = 0; r < 4; ++r) a.dhead[dhead_at(m, r)] = 0.0f;
+}
+// Piece (a) of a ray, first half: el[s] = exp(-relu(sigma) dist) and T[s], the exclusive running product, in the wave's two LDS rows.
+__device__ __forceinline__ void ray_transmittance(const CompositeArgs &a, int ray, int lane, float *el, float *T) {
     const int S = a.S;
-    const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S, *rr = a.raw_rgb + (size_t)ray * S * 3;
+    const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S;
     const float *nz = a.noise ? a.noise + (size_t)ray * S : nullptr;
     // el[s] = exp(-relu(sigma) dist): a_s = 1 - el[s] (:195), and the factor of the running product, (1 - a_s) + 1e-10 (:198), is taken as
     // el[s] + 1e-10 -- the value of the reference's expression without the float32 round trip through 1 - (1 - e), which on a saturated sample
     // (e ~ 1e-6) leaves 1 - a with two digits: the ray's transmittance, and with it every gradient behind the sample, would carry that error
-    float *el = sh_a[wave], *T = sh_T[wave];
     for (int s = lane; s < S; s += 64) { const float v = nz ? sg[s] + nz[s] : sg[s]; const float r = v > 0.0f ? v : 0.0f; el[s] = expf(-r * ds[s]); }    // :190-195
     __builtin_amdgcn_wave_barrier();
     // exclusive running product of (1 - a) + 1e-10, sequential like tf.math.cumprod (:198): chunks of 64 with a carry
@@ -97,7 +96,12 @@ __global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
         carry *= __shfl(incl, 63);
     }
     __builtin_amdgcn_wave_barrier();
-    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, A = 0.0f;
+}
+// Piece (a), second half: the ray's colour and opacity from el and T (every lane ends with them), and the optional weights a_i T_i.
+__device__ __forceinline__ void ray_composite(const CompositeArgs &a, int ray, int lane, const float *el, const float *T, float &c0, float &c1, float &c2, float &A) {
+    const int S = a.S;
+    const float *rr = a.raw_rgb + (size_t)ray * S * 3;
+    c0 = 0.0f; c1 = 0.0f; c2 = 0.0f; A = 0.0f;
     for (int s = lane; s < S; s += 64) {
         const float w = (1.0f - el[s]) * T[s];
         c0 += w * rgb_of(rr[3 * s], a.map_exr); c1 += w * rgb_of(rr[3 * s + 1], a.map_exr); c2 += w * rgb_of(rr[3 * s + 2], a.map_exr);
@@ -106,31 +110,22 @@ __global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
     }
     c0 = wave_sumf(c0); c1 = wave_sumf(c1); c2 = wave_sumf(c2); A = wave_sumf(A);
     if (a.composite_bkgd) { c0 += (1.0f - A) * a.bkgd[0]; c1 += (1.0f - A) * a.bkgd[1]; c2 += (1.0f - A) * a.bkgd[2]; }   // :210-211
-    // the ray's terms of the loss and their derivatives (loss.py:6-49)
-    const float cp[3] = {c0, c1, c2};
-    float dC[3], dA = 0.0f, total = 0.0f;
-    {
-        const float inv_c = 1.0f / (float)(a.n_rays * 3), inv_a = 1.0f / (float)a.n_rays;
-        float mask = 1.0f;
-        if (a.kind == NTX_LOSS_ALPHA && a.filter_color_loss) mask = a.use_hard_mask ? (a.alpha_true[ray] > 0.0f ? 1.0f : 0.0f) : a.alpha_true[ray];   // :29-35
-        for (int c = 0; c < 3; ++c) {
-            float v, gr;
-            loss_term(a.loss_fn, a.color_true[3 * ray + c] * mask, cp[c] * mask, inv_c, v, gr);
-            total += v; dC[c] = gr * mask;
-        }
-        if (a.kind == NTX_LOSS_ALPHA) { float v; loss_term(a.alpha_loss_fn, a.alpha_true[ray], A, inv_a, v, dA); total += a.gamma * v; dA *= a.gamma; }   // :38
-    }
-    if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; a.ray_loss[ray] = total; }
-    // adjoint.  C = sum w rgb (+ (1 - A) bkgd), A = sum w, w_i = a_i T_i, T_i = prod_{j<i} f_j, f_j = (1 - a_j) + 1e-10.  With
-    // dL/dw_k = c_k + dA' (c_k = dC . rgb_k, dA' = dA - dC . bkgd):
-    //     dL/da_i = T_i (dA' Z_i + (c_i - V_i)),
-    //     V_i = sum_{k>i} c_k a_k prod_{i<j<k} f_j   (the colour composited behind sample i, along dC):   V_{i-1} = c_i a_i + f_i V_i,  V_{S-1} = 0
-    //     Z_i = 1 - sum_{k>i} a_k prod_{i<j<k} f_j   (what is left of the ray behind sample i):            Z_{i-1} = f_i Z_i - 1e-10,   Z_{S-1} = 1
-    // Nothing is divided and the opacity term is never formed as a difference of two sums.  tf.math.cumprod's own gradient
-    // (TF 2.4 math_grad.py _CumprodGrad: cumsum(out * grad, reverse) / x) is the same derivative as a quotient by f_i, which on a saturated
-    // sample (f_i -> 1e-10) loses the digits the forward product kept, and "dA' (1 - sum)" loses them again when the ray saturates BEHIND
-    // sample i (round 5's kernel did both: profiles/r05/soak_train_seed3.txt, case 297).
-    // A chunk of 64 samples is a suffix scan of the affine maps X -> b_i + f_i X (composed pairwise), carried from chunk to chunk back to front.
+}
+// Piece (b): the adjoint of a ray's composite from dC = dL/d color_pred and dA = dL/d alpha_pred, to dgrad and its O-layout copy dhead.
+//     C = sum w rgb (+ (1 - A) bkgd), A = sum w, w_i = a_i T_i, T_i = prod_{j<i} f_j, f_j = (1 - a_j) + 1e-10.  With
+// dL/dw_k = c_k + dA' (c_k = dC . rgb_k, dA' = dA - dC . bkgd):
+//     dL/da_i = T_i (dA' Z_i + (c_i - V_i)),
+//     V_i = sum_{k>i} c_k a_k prod_{i<j<k} f_j   (the colour composited behind sample i, along dC):   V_{i-1} = c_i a_i + f_i V_i,  V_{S-1} = 0
+//     Z_i = 1 - sum_{k>i} a_k prod_{i<j<k} f_j   (what is left of the ray behind sample i):            Z_{i-1} = f_i Z_i - 1e-10,   Z_{S-1} = 1
+// Nothing is divided and the opacity term is never formed as a difference of two sums.  tf.math.cumprod's own gradient
+// (TF 2.4 math_grad.py _CumprodGrad: cumsum(out * grad, reverse) / x) is the same derivative as a quotient by f_i, which on a saturated
+// sample (f_i -> 1e-10) loses the digits the forward product kept, and "dA' (1 - sum)" loses them again when the ray saturates BEHIND
+// sample i (round 5's kernel did both: profiles/r05/soak_train_seed3.txt, case 297).
+// A chunk of 64 samples is a suffix scan of the affine maps X -> b_i + f_i X (composed pairwise), carried from chunk to chunk back to front.
+__device__ __forceinline__ void ray_adjoint(const CompositeArgs &a, int ray, int lane, const float *el, const float *T, const float (&dC)[3], float dA) {
+    const int S = a.S;
+    const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S, *rr = a.raw_rgb + (size_t)ray * S * 3;
+    const float *nz = a.noise ? a.noise + (size_t)ray * S : nullptr;
     if (a.composite_bkgd) dA -= (dC[0] * a.bkgd[0] + dC[1] * a.bkgd[1]) + dC[2] * a.bkgd[2];
     float Z_carry = 1.0f, V_carry = 0.0f;                  // Z, V of the last sample of the current chunk (nothing lies behind the ray's end)
     for (int s0 = ((S - 1) / 64) * 64; s0 >= 0; s0 -= 64) {
@@ -169,6 +164,66 @@ __global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
         const float F0 = __shfl(F, 0);
         Z_carry = fmaf(F0, Z_carry, __shfl(Bz, 0)); V_carry = fmaf(F0, V_carry, __shfl(Bv, 0));
     }
+}
+// the fused step's composite: (a), the ray's terms of the loss and their derivatives (loss.py:6-49), (b)
+__global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0) zero_dhead_tail(a);
+    const int ray = blockIdx.x * 4 + wave;
+    if (ray >= a.n_rays) return;
+    float *el = sh_a[wave], *T = sh_T[wave];
+    ray_transmittance(a, ray, lane, el, T);
+    float c0, c1, c2, A;
+    ray_composite(a, ray, lane, el, T, c0, c1, c2, A);
+    const float cp[3] = {c0, c1, c2};
+    float dC[3], dA = 0.0f, total = 0.0f;
+    {
+        const float inv_c = 1.0f / (float)(a.n_rays * 3), inv_a = 1.0f / (float)a.n_rays;
+        float mask = 1.0f;
+        if (a.kind == NTX_LOSS_ALPHA && a.filter_color_loss) mask = a.use_hard_mask ? (a.alpha_true[ray] > 0.0f ? 1.0f : 0.0f) : a.alpha_true[ray];   // :29-35
+        for (int c = 0; c < 3; ++c) {
+            float v, gr;
+            loss_term(a.loss_fn, a.color_true[3 * ray + c] * mask, cp[c] * mask, inv_c, v, gr);
+            total += v; dC[c] = gr * mask;
+        }
+        if (a.kind == NTX_LOSS_ALPHA) { float v; loss_term(a.alpha_loss_fn, a.alpha_true[ray], A, inv_a, v, dA); total += a.gamma * v; dA *= a.gamma; }   // :38
+    }
+    if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; a.ray_loss[ray] = total; }
+    ray_adjoint(a, ray, lane, el, T, dC, dA);
+}
+// ntx_train_forward's composite: (a) alone -- the predictions (and the weights a coarse pass hands on); nothing of the loss, no gradient
+__global__ __launch_bounds__(256) void composite_forward_kernel(CompositeArgs a) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ray = blockIdx.x * 4 + wave;
+    if (ray >= a.n_rays) return;
+    float *el = sh_a[wave], *T = sh_T[wave];
+    ray_transmittance(a, ray, lane, el, T);
+    float c0, c1, c2, A;
+    ray_composite(a, ray, lane, el, T, c0, c1, c2, A);
+    if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; }
+}
+// ntx_train_backward's composite: el and T again from what the pending forward left (sigma, dists, noise, raw_rgb), then (b) from the
+// caller's cotangents d_color [N][3] and d_alpha [N] (NULL: 0).  A ray whose depths are not finite has dists 0 throughout: it composites to
+// nothing, and its gradient is 0 whatever its cotangent holds (inf and NaN included) -- by selecting a zero cotangent for it, so that (b)
+// runs on the same numbers as with the cotangent zeroed by the caller, never by a product with what may not be finite.
+__global__ __launch_bounds__(256) void composite_adjoint_kernel(CompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0) zero_dhead_tail(a);
+    const int ray = blockIdx.x * 4 + wave;
+    if (ray >= a.n_rays) return;
+    float *el = sh_a[wave], *T = sh_T[wave];
+    ray_transmittance(a, ray, lane, el, T);
+    const float *ds = a.dists + (size_t)ray * a.S;
+    bool live = false;
+    for (int s = lane; s < a.S; s += 64) live = live || ds[s] != 0.0f;
+    live = __any(live) != 0;
+    float dC[3];
+    for (int c = 0; c < 3; ++c) dC[c] = live ? d_color[3 * ray + c] : 0.0f;
+    const float dA = live && d_alpha ? d_alpha[ray] : 0.0f;
+    ray_adjoint(a, ray, lane, el, T, dC, dA);
 }
 // the loss: the rays' terms added up by one workgroup in a fixed order
 __global__ __launch_bounds__(1024) void loss_sum_kernel(const float *__restrict__ ray_loss, int n_rays, float *__restrict__ loss) {
@@ -322,24 +377,23 @@ int ntx_trainer_allreduce_gradients(ntx_trainer *t, ntx_comm *comm, ntx_stream s
     return ntx_allreduce_mean_f32(comm, t->grad, t->n_weights, stream);
 }
 
-int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
-                             const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
-                             const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,
-                             float *color_pred, float *alpha_pred, float *loss_out, ntx_stream stream) {
-    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+// What the entries of a step share.  step_check: the rays and sizes of a step against the handle.  step_network: depths, noise and the
+// backend's forward (every activation kept); leaves the step's rays and the noise its composite takes (NULL without NTX_FLAG_RAW_NOISE).
+// composite_args: the composite's arguments less the loss and the cotangents.
+static int step_check(const ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, const float *cone_scale, int64_t n_rays,
+                      int n_samples, int blur_idx, const float *z_vals) {
     const int P_in = t->P + (t->ipe ? 1 : 0);                                               // the MipRenderer's rows still hold the blur parameter
-    if (!rays_o || !rays_d || (!tnear_far && !z_vals) || !color_true || !loss || (P_in > 0 && !params)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (!rays_o || !rays_d || (!tnear_far && !z_vals) || (P_in > 0 && !params)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
     if (n_rays < 1 || n_rays > t->cap_rays || n_samples < 2 || (long long)n_rays * n_samples > t->cap) return ntx_set_error(NTX_E_INVALID, "n_rays x n_samples beyond what the trainer was created for");
     if (n_samples > MAX_TRAIN_SAMPLES) return ntx_set_error(NTX_E_INVALID, "n_samples > %d", MAX_TRAIN_SAMPLES);
     if (blur_idx >= P_in || (blur_idx >= 0 && !cone_scale) || (t->ipe && blur_idx < 0)) return ntx_set_error(NTX_E_INVALID, "bad blur_idx / cone_scale");
-    if (loss->size < sizeof(ntx_loss_desc) || (loss->kind != NTX_LOSS_NERF && loss->kind != NTX_LOSS_ALPHA) || (loss->loss_fn != NTX_LOSS_MSE && loss->loss_fn != NTX_LOSS_SMAPE) ||
-        (loss->alpha_loss_fn != NTX_LOSS_MSE && loss->alpha_loss_fn != NTX_LOSS_SMAPE))
-        return ntx_set_error(NTX_E_INVALID, "bad ntx_loss_desc");
-    if (loss->kind == NTX_LOSS_ALPHA && !alpha_true) return ntx_set_error(NTX_E_INVALID, "AlphaLoss needs alpha_true");
+    return NTX_OK;
+}
+static int step_network(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
+                        const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, uint64_t perturb_seed, const ntx_render_opts *opts,
+                        const float *z_vals, ntx_stream stream, StepRays *rays, const float **noise) {
     if (rays_per_param_row < 1) rays_per_param_row = 1;
     TRAIN_TRY(hipSetDevice(t->device));
-    hipStream_t st = (hipStream_t)stream;
-    const long long M = (long long)n_rays * n_samples;
     const int S = n_samples;
     const float *z = z_vals;                                                                    // [N][S], or the S + 1 segment edges of a mip step
     if (!z) {
@@ -347,31 +401,89 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
         if (rc != NTX_OK) return rc;
         z = t->z;
     }
-    const float *noise = nullptr;
+    *noise = nullptr;
     if (flags & NTX_FLAG_RAW_NOISE) {                                                           // renderer.py:190-192
         int rc = ntx_sample_noise(n_rays, S, perturb_seed, opts, t->noise, stream);
         if (rc != NTX_OK) return rc;
-        noise = t->noise;
+        *noise = t->noise;
     }
     const ntx_model_desc &d = t->desc;
-    const StepRays rays{rays_o, rays_d, z, params, cone_scale, rays_per_param_row, n_rays, S, blur_idx, d.n_geo, d.n_app, d.pos_freq, d.dir_freq, d.param_freq};
-    int rc = t->backend->forward(rays, st);                                                     // every activation kept
-    if (rc != NTX_OK) return rc;
-    // ---- the composite, the loss (loss.py) and their adjoint ------------------------------------------------------------------------
+    *rays = StepRays{rays_o, rays_d, z, params, cone_scale, rays_per_param_row, n_rays, S, blur_idx, d.n_geo, d.n_app, d.pos_freq, d.dir_freq, d.param_freq};
+    return t->backend->forward(*rays, (hipStream_t)stream);
+}
+static CompositeArgs composite_args(const ntx_trainer *t, const StepRays &rays, const float *noise, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred) {
     CompositeArgs c{};
-    c.raw_rgb = t->raw_rgb; c.sigma = t->sigma; c.dists = t->dists; c.noise = noise; c.n_rays = (int)n_rays; c.S = S; c.map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0;
+    c.raw_rgb = t->raw_rgb; c.sigma = t->sigma; c.dists = t->dists; c.noise = noise; c.n_rays = (int)rays.n_rays; c.S = rays.S; c.map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0;
     c.composite_bkgd = (flags & NTX_FLAG_COMPOSITE_BKGD) ? 1 : 0;
     for (int k = 0; k < 3; ++k) c.bkgd[k] = bkgd ? bkgd[k] : 1.0f;
+    c.weights = t->weights_out;
+    c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.ray_loss = t->ray_loss; c.dgrad = t->dgrad; c.dhead = t->dhead; c.M = rays.M();
+    return c;
+}
+
+int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
+                             const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
+                             const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,
+                             float *color_pred, float *alpha_pred, float *loss_out, ntx_stream stream) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    t->pending.open = false;                                                                    // a forward left open is not this step's
+    if (!color_true || !loss) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (int rc = step_check(t, rays_o, rays_d, tnear_far, params, cone_scale, n_rays, n_samples, blur_idx, z_vals)) return rc;
+    if (loss->size < sizeof(ntx_loss_desc) || (loss->kind != NTX_LOSS_NERF && loss->kind != NTX_LOSS_ALPHA) || (loss->loss_fn != NTX_LOSS_MSE && loss->loss_fn != NTX_LOSS_SMAPE) ||
+        (loss->alpha_loss_fn != NTX_LOSS_MSE && loss->alpha_loss_fn != NTX_LOSS_SMAPE))
+        return ntx_set_error(NTX_E_INVALID, "bad ntx_loss_desc");
+    if (loss->kind == NTX_LOSS_ALPHA && !alpha_true) return ntx_set_error(NTX_E_INVALID, "AlphaLoss needs alpha_true");
+    hipStream_t st = (hipStream_t)stream;
+    StepRays rays{};
+    const float *noise = nullptr;
+    int rc = step_network(t, rays_o, rays_d, tnear_far, params, rays_per_param_row, cone_scale, n_rays, n_samples, blur_idx, flags, perturb_seed, opts, z_vals, stream, &rays, &noise);
+    if (rc != NTX_OK) return rc;
+    // ---- the composite, the loss (loss.py) and their adjoint ------------------------------------------------------------------------
+    CompositeArgs c = composite_args(t, rays, noise, flags, bkgd, color_pred, alpha_pred);
     c.color_true = color_true; c.alpha_true = alpha_true; c.kind = loss->kind; c.loss_fn = loss->loss_fn; c.alpha_loss_fn = loss->alpha_loss_fn;
     c.filter_color_loss = loss->filter_color_loss; c.use_hard_mask = loss->use_hard_mask; c.gamma = loss->gamma;
-    c.weights = t->weights_out;
-    c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.ray_loss = t->ray_loss; c.dgrad = t->dgrad; c.dhead = t->dhead; c.M = M;
     hipLaunchKernelGGL(composite_loss_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, st, c);
     hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, t->ray_loss, (int)n_rays, loss_out ? loss_out : t->loss);
     rc = t->backend->backward(rays, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
-    if (t->pg_mode != 0) t->pg_rows = (n_rays + rays_per_param_row - 1) / rays_per_param_row;
+    if (t->pg_mode != 0) t->pg_rows = (n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row;
+    return NTX_OK;
+}
+
+int ntx_train_forward(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
+                      const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
+                      const ntx_render_opts *opts, const float *z_vals, float *color_pred, float *alpha_pred, ntx_stream stream) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    t->pending.open = false;                                                                    // a new forward replaces the one left open
+    if (int rc = step_check(t, rays_o, rays_d, tnear_far, params, cone_scale, n_rays, n_samples, blur_idx, z_vals)) return rc;
+    StepRays rays{};
+    const float *noise = nullptr;
+    int rc = step_network(t, rays_o, rays_d, tnear_far, params, rays_per_param_row, cone_scale, n_rays, n_samples, blur_idx, flags, perturb_seed, opts, z_vals, stream, &rays, &noise);
+    if (rc != NTX_OK) return rc;
+    const CompositeArgs c = composite_args(t, rays, noise, flags, bkgd, color_pred, alpha_pred);
+    hipLaunchKernelGGL(composite_forward_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c);
+    TRAIN_TRY(hipGetLastError());
+    t->pending.rays = rays; t->pending.flags = flags; t->pending.noise = noise;
+    for (int k = 0; k < 3; ++k) t->pending.bkgd[k] = c.bkgd[k];
+    t->pending.open = true;
+    return NTX_OK;
+}
+
+int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alpha, ntx_stream stream) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    if (!t->pending.open) return ntx_set_error(NTX_E_INVALID, "no ntx_train_forward is pending (one ntx_train_backward per forward; ntx_train_step_gradients closes it too)");
+    if (!d_color) return ntx_set_error(NTX_E_INVALID, "d_color is NULL");
+    t->pending.open = false;
+    TRAIN_TRY(hipSetDevice(t->device));
+    const StepRays &rays = t->pending.rays;
+    CompositeArgs c = composite_args(t, rays, t->pending.noise, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
+    c.weights = nullptr;                                                                        // (b) alone: nothing of the forward is written again
+    hipLaunchKernelGGL(composite_adjoint_kernel, dim3((unsigned)((rays.n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c, d_color, d_alpha);
+    int rc = t->backend->backward(rays, (hipStream_t)stream);
+    if (rc != NTX_OK) return rc;
+    TRAIN_TRY(hipGetLastError());
+    if (t->pg_mode != 0) t->pg_rows = (rays.n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row;
     return NTX_OK;
 }
 

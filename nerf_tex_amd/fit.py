@@ -8,7 +8,8 @@ target images it finds the parameters that reproduce them, by gradient descent o
 The gradient is the layer-by-layer trainer's dL/d parameters in its parameters-only mode (`ntx_trainer_enable_param_gradients` mode 2: the
 forward pass, the composite's adjoint and the way back through the activations, no weight gradient); the update of the handful of
 parameters is `torch.optim.Adam` on the device.  Positions and directions take no gradient; an IPE model and a coarse + fine pair are not
-taken."""
+taken.  `loss`: a `nerf_tex_amd.loss` object, or any callable `loss(color_true=, alpha_true=, color_pred=, alpha_pred=)` on torch tensors that
+returns a scalar -- a robust loss for photographs, say (`Trainer.gradients_step`)."""
 
 from __future__ import annotations
 

@@ -3,7 +3,12 @@
 Same names, same constructor keywords: a training config's `loss_config` ({'module': 'network.loss.AlphaLoss', 'loss_fn':
 'network.loss.smape', 'alpha_loss_fn': 'network.loss.mse'}, configs/config_carpet_train.py:95-99) instantiates these through
 `util.remap_reference_config`.  A loss object is not called on tensors here -- value and gradient come out of the fused step -- it carries
-`desc()`, the `ntx_loss_desc` of its settings."""
+`desc()`, the `ntx_loss_desc` of its settings.
+
+Any OTHER loss is written in PyTorch: `Trainer.gradients_step`, `Train` and `ParameterFitter.fit` take an object without `desc()` as a callable
+`loss(color_true=, alpha_true=, color_pred=, alpha_pred=) -> scalar tensor` (the reference's call, loss.py:12, 30; a `loss_config` names its
+class by module path) and run the step as `ntx_train_forward`, the loss and its two cotangents in torch, `ntx_train_backward`
+(`nerf_tex_amd.autograd` is the same as a differentiable op)."""
 
 from __future__ import annotations
 

@@ -18,7 +18,9 @@ contraction per Dense layer and pass (`ntx_trainer_create_flex`); `BranchTrainer
 (param_depth 1..4, param_width 2..128: `ntx_trainer_create_flex_ex`).  `trainer_for(model, ...)` picks between them, and
 `Trainer.from_config`, `CoarseFineTrainer` and `Train` build their trainers through it.  The layer-by-layer trainers also take the one
 gradient a training step otherwise leaves out, dL/d material parameters (`param_gradients=`, `parameter_gradients()`); `nerf_tex_amd.fit`
-fits parameters to target images with it."""
+fits parameters to target images with it.  The losses of `nerf_tex_amd.loss` are evaluated inside the step; any other loss is a callable on
+torch tensors, and the step runs as `forward(...)`, the loss and its two cotangents in torch, `backward(d_color, d_alpha)`
+(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op)."""
 
 from __future__ import annotations
 
@@ -65,6 +67,7 @@ class Trainer:
         self.n_weights = self._n_native if self._pad is None else int(self._pad.size)
         self._calls = 0
         self._last_rays = 0
+        self._pending, self._forwards = None, 0                                 # (serial, rays, device tensors) of a `forward` whose `backward` has not run
 
     _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create(*a))           # the entry that makes the native trainer
     _widen = staticmethod(lambda model: _widened(model))                           # a narrower network inside the 256-wide one
@@ -206,14 +209,40 @@ class Trainer:
                        seed: Optional[int] = None, z_vals=None, rays_per_param_row: int = 1, n_samples: Optional[int] = None):
         """Forward + loss + gradients (train.py:61-66): rays_o / rays_d [N,3], t [N,2] (inf for a ray that misses the proxy: it predicts 0 / the
         background and counts in the loss, renderer.py:58-86), parameters [rows,P],
-        cone_scale [N] or [N,1], color_true [N,3], alpha_true [N]; `loss`: a nerf_tex_amd.loss object.  Returns (loss [1], color_pred [N,3],
+        cone_scale [N] or [N,1], color_true [N,3], alpha_true [N]; `loss`: a nerf_tex_amd.loss object (the fused step), or any callable
+        `loss(color_true=, alpha_true=, color_pred=, alpha_pred=)` on torch tensors that returns a scalar (`forward`, torch, `backward`: the same
+        gradients for ANY differentiable loss of the predictions).  Returns (loss [1], color_pred [N,3],
         alpha_pred [N]) as GPU tensors; the gradients stay in the trainer.  `z_vals` [N, n_samples]: given sample depths (`n_samples` of them,
         default the trainer's) instead of the ones placed between t.  An IPE trainer (MipRenderer): parameters [rows, P + 1] with the blur parameter
         at blur_idx, `z_vals` [N, n_samples + 1] segment edges."""
         import torch
+        if not hasattr(loss, "desc"):                                          # a loss written in PyTorch: forward, the loss and its cotangents in torch, backward
+            return self._callable_loss_step(rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, loss, composite_bkgd=composite_bkgd, bkgd_color=bkgd_color,
+                                            seed=seed, z_vals=z_vals, rays_per_param_row=rays_per_param_row, n_samples=n_samples)
+        self._pending = None                                                   # (the fused step drops a forward left open)
+        dev, to, ptr = self._device_tools()
+        color_true, alpha_true = to(color_true), to(alpha_true)
+        n, head, tail, keep = self._step_inputs(rays_o, rays_d, t, parameters, cone_scale, composite_bkgd, bkgd_color, seed, z_vals, rays_per_param_row, n_samples)   # keep: alive over the call
+        color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev); val = torch.empty((1,), device=dev)
+        desc = loss.desc()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.ntx_train_step_gradients(self._h, *head, *tail, ptr(color_true), ptr(alpha_true), C.byref(desc), ptr(color), ptr(alpha), ptr(val),
+                                                         torch.cuda.current_stream(dev).cuda_stream))
+        return val, color, alpha
+
+    def _device_tools(self):
+        import torch
         dev = torch.device("cuda", self.device)
         to = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32).contiguous()
-        rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, z_vals = (to(a) for a in (rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, z_vals))
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+        return dev, to, ptr
+
+    def _step_inputs(self, rays_o, rays_d, t, parameters, cone_scale, composite_bkgd, bkgd_color, seed, z_vals, rays_per_param_row, n_samples):
+        """What `ntx_train_step_gradients` and `ntx_train_forward` share: the number of rays, the arguments up to blur_idx (`head`) and from the
+        flags to z_vals (`tail`), and the device tensors behind the pointers (to be kept while the library reads them).  Counts the call: the
+        default jitter / noise seed is the number of steps taken."""
+        _, to, ptr = self._device_tools()
+        rays_o, rays_d, t, parameters, cone_scale, z_vals = (to(a) for a in (rays_o, rays_d, t, parameters, cone_scale, z_vals))
         n = rays_o.reshape(-1, 3).shape[0]
         P_in = int(getattr(self.model, "n_params", 0)) + (1 if self.mip else 0)
         if P_in > 0 and parameters is not None:                                # the kernels read row ray // rays_per_param_row of it unasked: a count of floats, no shape test
@@ -230,15 +259,65 @@ class Trainer:
         if seed is None:
             seed = self._calls
         self._calls += 1
-        color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev); val = torch.empty((1,), device=dev)
-        desc = loss.desc()
-        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+        head = (ptr(rays_o), ptr(rays_d), ptr(t), ptr(parameters), int(rays_per_param_row), ptr(cone_scale), n, int(n_samples or self.n_samples),
+                -1 if self.blur_idx is None else int(self.blur_idx))
+        tail = (flags, _lib.f3(bkgd_color), int(seed) & (2 ** 64 - 1), opts, ptr(z_vals))
+        return n, head, tail, (rays_o, rays_d, t, parameters, cone_scale, z_vals)
+
+    def forward(self, rays_o, rays_d, t, parameters, cone_scale, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.), seed: Optional[int] = None, z_vals=None,
+                rays_per_param_row: int = 1, n_samples: Optional[int] = None):
+        """The first half of a step under any loss (`ntx_train_forward`): `gradients_step`'s arguments less the targets and the loss; returns
+        (color_pred [N,3], alpha_pred [N]) as GPU tensors -- bit for bit `gradients_step`'s -- and leaves the step pending until
+        `backward(d_color, d_alpha)`.  The trainer keeps the batch's device tensors until then; a tensor handed in that is already float32,
+        contiguous and on the device is read in place and must not be written before the backward."""
+        import torch
+        dev, _, ptr = self._device_tools()
+        self._pending = None
+        n, head, tail, keep = self._step_inputs(rays_o, rays_d, t, parameters, cone_scale, composite_bkgd, bkgd_color, seed, z_vals, rays_per_param_row, n_samples)
+        color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib.ntx_train_step_gradients(
-                self._h, ptr(rays_o), ptr(rays_d), ptr(t), ptr(parameters), int(rays_per_param_row), ptr(cone_scale), n, int(n_samples or self.n_samples),
-                -1 if self.blur_idx is None else int(self.blur_idx), flags, _lib.f3(bkgd_color), int(seed) & (2 ** 64 - 1), opts, ptr(z_vals), ptr(color_true), ptr(alpha_true),
-                C.byref(desc), ptr(color), ptr(alpha), ptr(val), torch.cuda.current_stream(dev).cuda_stream))
-        return val, color, alpha
+            _lib.check(_lib.lib.ntx_train_forward(self._h, *head, *tail, ptr(color), ptr(alpha), torch.cuda.current_stream(dev).cuda_stream))
+        self._forwards += 1
+        self._pending = (self._forwards, n, keep)
+        return color, alpha
+
+    def backward(self, d_color, d_alpha=None) -> None:
+        """The second half (`ntx_train_backward`): `d_color` [N,3] = dL/d color_pred and `d_alpha` [N] = dL/d alpha_pred (None: 0) of the pending
+        `forward` -> the gradients of L, left in the trainer exactly as `gradients_step` leaves them (`gradients()`, `sync_gradients`,
+        `apply_gradients`, `parameter_gradients()`).  One backward per forward: NTX_E_INVALID without a pending forward, or after a
+        `gradients_step` in between.  Every gradient is linear in the two cotangents, so L is any differentiable function of the predictions;
+        a data-parallel mean of gradients (`sync_gradients`) is the gradient of the ranks' joint loss only if L is a mean over rays."""
+        import torch
+        dev, to, ptr = self._device_tools()
+        pending, self._pending = self._pending, None
+        d_color, d_alpha = to(d_color), to(d_alpha)
+        if pending is not None and d_color is not None:
+            n = pending[1]
+            if d_color.numel() != 3 * n or (d_alpha is not None and d_alpha.numel() != n):
+                self._pending = pending
+                raise ValueError(f"d_color / d_alpha hold {d_color.numel()} / {None if d_alpha is None else d_alpha.numel()} floats, the pending forward has {n} rays")
+        with torch.cuda.device(dev):
+            rc = _lib.lib.ntx_train_backward(self._h, d_color.data_ptr() if d_color is not None else None, ptr(d_alpha), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.NTX_OK and d_color is None:
+            self._pending = pending                                            # (the library keeps the forward open on a NULL d_color)
+        _lib.check(rc)
+
+    def _callable_loss_step(self, rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, loss, **kw):
+        """`gradients_step` for a loss without `desc()`: any callable `loss(color_true=, alpha_true=, color_pred=, alpha_pred=)` on torch tensors
+        that returns a scalar (the reference's call, loss.py:12, 30).  Its value and its gradient at the predictions come from torch's autograd,
+        everything else from the native forward and backward."""
+        import torch
+        _, to, _ = self._device_tools()
+        color_true, alpha_true = to(color_true), to(alpha_true)
+        color, alpha = self.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
+        c, a = color.detach().requires_grad_(True), alpha.detach().requires_grad_(True)
+        with torch.enable_grad():
+            val = loss(color_true=color_true, alpha_true=alpha_true, color_pred=c, alpha_pred=a)
+            if not isinstance(val, torch.Tensor) or val.numel() != 1:
+                raise TypeError("a loss without desc() must return a scalar tensor")
+            d_color, d_alpha = torch.autograd.grad(val.reshape(()), (c, a), allow_unused=True)
+        self.backward(torch.zeros_like(color) if d_color is None else d_color, d_alpha)
+        return val.detach().reshape(1), color, alpha
 
     def apply_gradients(self) -> None:
         """optimizer.apply_gradients (train.py:67): Adam under the learning-rate schedule of train.py:49-52."""
@@ -463,6 +542,9 @@ class CoarseFineTrainer:
         `u` [N, n_importance]: the sampler's uniform draws when perturb is off (renderer.py:128 `det=self.perturb`: with perturb they are
         tf.linspace); default: torch's generator under `seed`.  `on_coarse()`: called between the passes (tests read the coarse activations)."""
         import torch
+        if not hasattr(loss, "desc"):
+            raise TypeError("a coarse + fine step takes a nerf_tex_amd.loss object: a loss written in PyTorch would need the cotangents of two passes "
+                            "(Trainer.forward / backward and nerf_tex_amd.autograd.DifferentiableRender are one pass)")
         dev = torch.device("cuda", self.device)
         to = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32).contiguous()
         rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true = (to(a) for a in (rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true))
