@@ -650,6 +650,46 @@ int ntx_train_forward(ntx_trainer *t, const float *rays_o, const float *rays_d, 
                       const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
                       const ntx_render_opts *opts, const float *z_vals, float *color_pred, float *alpha_pred, ntx_stream stream);
 int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alpha, ntx_stream stream);
+/* The differentiable InstanceRenderer tail (ABI v7, appended): ntx_train_forward for the instanced render -- InstanceRenderer.evaluate_model +
+ * map_model_output (renderer.py:247-354, inference-only in the reference: :233) downstream of the instancer, exactly as
+ * ntx_render_instanced documents them, with every activation kept, so that a network is trained, or a parameter field fitted, in the
+ * scene it is rendered in.  For a handle of ntx_trainer_create_flex / ntx_trainer_create_flex_ex (parameter branches included);
+ * NTX_E_UNSUPPORTED for one of ntx_trainer_create (the fused chain runs on whole rays; the layer-by-layer entries take the same model).
+ * The arguments are ntx_render_instanced's buffers (DEVICE): rays_d_map[N,S,3], pts[N,S,3], t_map[N,S], dists[N,S], color_last[N,3],
+ * alpha_last[N], alpha_weight[N,S] (NULL = density_reweighting off), hit[N] uint8, params_map[N,S,P] (NULL when P == 0), cone_scale[N]
+ * (with t_map needed only for blur_idx >= 0).  Sample (r, s) is LIVE iff hit[r] != 0 && dists[r,s] > 0.  A live sample's network inputs:
+ * pts, rays_d_map as given (not normalised), params_map with column blur_idx times cone_scale[r] * t_map[r,s] / patch_scale (:259-263);
+ * its composite: sigma' = sigma * alpha_weight * density_scale, a = 1 - exp(-relu(sigma') * dists / patch_scale), colour sigmoid or -- under
+ * NTX_FLAG_MAP_EXR -- elu + 1.  A sample that is not live has a = 0 exactly (its factor of the running product is 1 + 1e-10, as in the
+ * reference), and NOTHING is read from pts, rays_d_map, t_map, alpha_weight or params_map there (the sparse instancer leaves those
+ * elements unwritten).  One appended sample (color_last as is, alpha_last as an alpha) closes every hit ray; NTX_FLAG_COMPOSITE_BKGD as in
+ * the render entry; a ray with hit == 0 predicts 0 / 0 also under the background and takes no gradient whatever its cotangent holds (NaN
+ * and inf included: it is never read).
+ * COMPACTION: the live samples are numbered in ascending (ray, sample) order by a prefix sum in two levels -- a function of hit and dists
+ * alone, no atomic decides an order -- and the network runs on those n_live rows only: the encoder, every layer's contraction forward and
+ * back, the heads, the weight gradients' partial sums over ranges of 2048 ROWS; ntx_trainer_activation's rows are the compact rows.  The
+ * launches are sized on the host, so the forward copies the count back (8 bytes) and waits for `stream`: the ONE synchronisation of the
+ * step.  *n_live_out (HOST, may be NULL) receives it.  n_live = 0 is a legal step: the predictions come from the appended sample alone,
+ * every weight gradient is exactly 0 and no contraction is launched.  A step's gradients do not depend on the trainer's capacity.
+ * The step is then PENDING as ntx_train_forward's, under the same CONTRACT: the caller keeps all buffers alive and unchanged until
+ * ntx_train_backward(t, d_color, d_alpha, stream) -- one backward per forward; a new forward of either kind or an ntx_train_step_gradients
+ * replaces a pending one; a NULL d_color leaves it pending.  The backward: ray_adjoint's recurrences with the appended sample behind sample
+ * S - 1 (the carries start at V = (dC . color_last) alpha_last, Z = ((1 - alpha_last) + 1e-10) - 1e-10); dL/d sigma of a live sample =
+ * d_a * (dists / patch_scale) * e * alpha_weight * density_scale where sigma' > 0; color_last, alpha_last, alpha_weight, positions and
+ * directions take no gradient.
+ * dL/d params (ntx_trainer_enable_param_gradients mode 1 / 2, semantics unchanged): an instanced step leaves PER-SAMPLE gradients
+ * grad_dev[N][S][P] (geometry columns first; through FourierFeatures and, for blur_idx, times cone_scale * t / patch_scale; exact zeros at
+ * samples that are not live) behind ntx_trainer_sample_param_gradients (DEVICE memory of the trainer, valid until the next step;
+ * NTX_E_INVALID after a plain step or in mode 0); ntx_trainer_param_gradients returns NTX_E_INVALID after an instanced step.
+ * NTX_E_INVALID: n_samples outside 1 .. 1024, n_rays / n_rays * n_samples beyond the trainer's capacity, patch_scale <= 0, blur_idx >= P,
+ * blur_idx >= 0 without cone_scale or t_map, NTX_FLAG_PERTURB or NTX_FLAG_RAW_NOISE (the instancer places the samples; noise is out of
+ * scope), a required buffer NULL.  Out of scope: IPE models, false colours, coarse + fine. */
+int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const float *pts, const float *t_map, const float *dists,
+                                const float *color_last, const float *alpha_last, const float *alpha_weight, const uint8_t *hit,
+                                const float *params_map, const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx,
+                                float patch_scale, float density_scale, uint32_t flags, const float *bkgd, float *color_pred,
+                                float *alpha_pred, int64_t *n_live_out, ntx_stream stream);
+int ntx_trainer_sample_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *n_rays, int *n_samples, int *n_params);
 
 #ifdef __cplusplus
 }

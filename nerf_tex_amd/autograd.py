@@ -13,7 +13,10 @@ Every gradient of a step is linear in dL/d color_pred and dL/d alpha_pred, so au
 
 One backward per forward (the activations are the trainer's, not the graph's), first order only: nothing differentiates the backward.  A
 data-parallel mean of the ranks' gradients is the gradient of their joint loss only when that loss is a mean over rays.  A coarse + fine
-pair is two passes with two sets of cotangents and is not taken."""
+pair is two passes with two sets of cotangents and is not taken.
+
+`DifferentiableInstanceRender` is the same op on the instanced render (InstanceRenderer's tail on an instancer's buffers), with the per-sample
+parameter field `params_map` [N, S, P] in the place of `parameters`."""
 
 from __future__ import annotations
 
@@ -40,6 +43,39 @@ class DifferentiableRender:
         return _render_function().apply(anchor, parameters if wants else None, tr, (rays_o, rays_d, t, parameters, cone_scale), kw)
 
 
+class DifferentiableInstanceRender:
+    """The same op on the INSTANCED render (`FlexTrainer.forward_instanced`, `ntx_train_forward_instanced`): fine-tune a network in the scene
+    it is rendered in, or fit a parameter field to an image of the furred object.
+
+        render = DifferentiableInstanceRender(trainer, patch_scale=0.09, density_scale=400.)   # a FlexTrainer or BranchTrainer
+        color_pred, alpha_pred = render(bufs, cone_scale, params_map=field)                    # bufs: the instancer's ten-tuple
+        (my_loss(color_pred, alpha_pred) + 1e-3 * field.square().sum()).backward()             # field.grad [N,S,P] from both terms
+
+    `params_map` (default: the tuple's) that requires grad receives the per-sample gradient (zero outside every patch); that needs
+    `param_gradients` on.  The weight gradient stays in the trainer.  One backward per forward, as `DifferentiableRender`."""
+
+    def __init__(self, trainer, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True) -> None:
+        if not hasattr(trainer, "forward_instanced"):
+            raise TypeError("DifferentiableInstanceRender takes a layer-by-layer trainer (FlexTrainer, BranchTrainer): the fused chain runs on whole rays")
+        self.trainer = trainer
+        self.opts = dict(patch_scale=float(patch_scale), density_scale=float(density_scale), density_reweighting=bool(density_reweighting))
+
+    def __call__(self, bufs, cone_scale, params_map=None, **kw):
+        """`FlexTrainer.forward_instanced`'s arguments (composite_bkgd, bkgd_color, hit in `kw`); returns (color_pred [N,3], alpha_pred [N]) in
+        the autograd graph."""
+        import torch
+        tr = self.trainer
+        bufs = tuple(bufs)
+        if params_map is None:
+            params_map = bufs[9]
+        wants = isinstance(params_map, torch.Tensor) and params_map.requires_grad
+        if wants and not getattr(tr, "param_gradients", False):
+            raise ValueError("params_map.requires_grad, but the trainer takes no parameter gradients (FlexTrainer / BranchTrainer with param_gradients=True or \"only\"); "
+                             "detach it, or its gradient would silently lack the render's term")
+        anchor = torch.zeros((), device=torch.device("cuda", tr.device), requires_grad=True)
+        return _render_function().apply(anchor, params_map if wants else None, tr, ("instanced", bufs[:9] + (params_map,), cone_scale), dict(self.opts, **kw))
+
+
 @functools.lru_cache(maxsize=None)
 def _render_function():
     """The torch.autograd.Function behind `DifferentiableRender` (made at the first call: importing the package does not import torch)."""
@@ -48,10 +84,16 @@ def _render_function():
     class Render(torch.autograd.Function):
         @staticmethod
         def forward(ctx, anchor, held, trainer, args, kw):
-            rays_o, rays_d, t, parameters, cone_scale = args
-            if isinstance(parameters, torch.Tensor):
-                parameters = parameters.detach()
-            color, alpha = trainer.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
+            ctx.instanced = len(args) == 3 and isinstance(args[0], str)
+            if ctx.instanced:                                        # ("instanced", the instancer's ten buffers, cone_scale)
+                _, bufs, cone_scale = args
+                bufs = tuple(b.detach() if isinstance(b, torch.Tensor) else b for b in bufs)
+                color, alpha = trainer.forward_instanced(bufs, cone_scale, **kw)
+            else:
+                rays_o, rays_d, t, parameters, cone_scale = args
+                if isinstance(parameters, torch.Tensor):
+                    parameters = parameters.detach()
+                color, alpha = trainer.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
             ctx.trainer, ctx.serial, ctx.like = trainer, trainer._pending[0], (None if held is None else (tuple(held.shape), held.device, held.dtype))
             return color, alpha
 
@@ -65,8 +107,11 @@ def _render_function():
                                    "run another step since (its activations are the trainer's, not the graph's)")
             tr.backward(d_color, d_alpha)
             grad = None
-            if ctx.like is not None:
-                rows = tr.parameter_gradients()                       # [rows the step read, P]; rows of `parameters` behind them were not read
+            if ctx.like is not None and ctx.instanced:
+                shape, device, dtype = ctx.like
+                grad = tr.sample_parameter_gradients().reshape(shape).to(device=device, dtype=dtype)   # [N, S, P], zero outside every patch
+            elif ctx.like is not None:
+                rows = tr.parameter_gradients()                      # [rows the step read, P]; rows of `parameters` behind them were not read
                 shape, device, dtype = ctx.like
                 grad = torch.zeros(shape, device=rows.device, dtype=rows.dtype)
                 grad.reshape(-1)[:rows.numel()].copy_(rows.reshape(-1))

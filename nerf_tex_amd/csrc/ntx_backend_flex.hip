@@ -2,8 +2,9 @@
 // ParamNerf the flex render family takes (other depths, widths, skips, color_depth; through the _ex entry also param_depth > 0) on row-major
 // activations -- flex_encode_kernel, one contraction (ntx_gemm.hip) per Dense layer and pass, the narrow heads on flex_head_*_kernel, a
 // parameter branch's output into the concatenations by flex_branch_copy_kernel; where it is asked for (ntx_trainer_enable_param_gradients), dL/d params:
-// one more term per reader of the parameter features, then flex_param_fold_kernel / flex_param_rows_kernel.  The handle, the composite, the loss and Adam are
-// ntx_trainer.hip's.  gfx950 only.
+// one more term per reader of the parameter features, then flex_param_fold_kernel / flex_param_rows_kernel.  An instanced step
+// (ntx_train_forward_instanced) is the same network on the compact rows of the in-patch samples: flex_encode_samples_kernel in front,
+// flex_param_samples_kernel behind.  The handle, the composite, the loss and Adam are ntx_trainer.hip's.  gfx950 only.
 #include <algorithm>
 #include "ntx_trainer.h"
 #include "ntx_encode.h"
@@ -47,6 +48,36 @@ __global__ __launch_bounds__(256) void flex_encode_kernel(FlexEncodeArgs args) {
         args.dir.p[(size_t)m * args.dir.ld + f] = v;
         if (f == 0) args.dists[(size_t)ray * a.S + s] = sample_dist(zray, s, a.S, z, hit, rc.dn);
     }
+}
+
+// The same rows for an instanced step (ntx_train_forward_instanced): row i of every destination is live sample m = live[i] of the
+// instancer's buffers -- position pts[m], direction rays_d_map[m] as given (renderer.py:265-272 hands it on un-normalised), parameters
+// params_map[m], blur_idx's times cone_scale t / patch_scale (:259-263).  Thread per compact row and feature, blockIdx.y = the map; the
+// values are ntx_encode.h's fourier_row, as the render side's.  Only live samples are read; the distances stay the caller's.
+struct FlexEncodeSamplesArgs {
+    StepSamples s; int Kp, Kd;
+    FlexDst pos[FLEX_MAX_DST], dir; int n_pos_dst;
+    FlexDst geo_in, app_in;
+};
+__global__ __launch_bounds__(256) void flex_encode_samples_kernel(FlexEncodeSamplesArgs args) {
+    const StepSamples &a = args.s;
+    const int part = blockIdx.y, K = part == 0 ? args.Kp : args.Kd, P = a.n_geo + a.n_app;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.n_live * K) return;
+    const long long i = e / K, m = a.live[i], ray = m / a.S;
+    const int f = (int)(e - i * K);
+    const int K3 = fourier_width(3, part == 0 ? a.pos_freq : a.dir_freq);
+    const bool xyz = f < K3;
+    const float v = fourier_row(xyz ? f : f - K3, xyz ? 3 : (part == 0 ? a.n_geo : a.n_app), [&](int c) -> float {
+        if (xyz) return (part == 0 ? a.pts : a.rays_d_map)[3 * m + c];
+        const int col = part == 0 ? c : a.n_geo + c;
+        const float p = a.params_map[(size_t)m * P + col];
+        return col == a.blur_idx ? p * a.blur_scale(m, ray) : p;
+    });
+    const FlexDst &branch = part == 0 ? args.geo_in : args.app_in;
+    if (!xyz && branch.p) branch.p[(size_t)i * branch.ld + (f - K3)] = v;
+    else if (part == 0) for (int q = 0; q < args.n_pos_dst; ++q) args.pos[q].p[(size_t)i * args.pos[q].ld + f] = v;
+    else args.dir.p[(size_t)i * args.dir.ld + f] = v;
 }
 
 // The output of a parameter branch's last layer, src[m][c] for c < width, behind the FF(xyz) columns of every buffer that starts with the map
@@ -196,6 +227,33 @@ __global__ __launch_bounds__(256) void flex_param_rows_kernel(const float *__res
     for (long long r = r0; r < r1; ++r) sum += ray_pg[(size_t)r * P + c];
     out[e] = sum;
 }
+// The fold of an instanced step: nothing is added up -- every sample has parameters of its own (params_map), so out[m][c] is live sample m's
+// row of PG (compact row row_of[m]) through the same derivative, times cone_scale t / patch_scale for blur_idx; a sample that is not live
+// is written as 0 and nothing of it is read.  Thread per (sample, parameter).
+struct FlexSampleFoldArgs { StepSamples s; const float *pg_geo, *pg_app; int ld_geo, ld_app; float *out; };       // out [N][S][P], geometry columns first
+__global__ __launch_bounds__(256) void flex_param_samples_kernel(FlexSampleFoldArgs args) {
+    const StepSamples &a = args.s;
+    const int P = a.n_geo + a.n_app;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.M() * P) return;
+    const long long m = e / P;
+    const int c = (int)(e - m * P), row_i = a.row_of[m];
+    float v = 0.0f;
+    if (row_i >= 0) {
+        const bool geo = c < a.n_geo;
+        const int D = geo ? a.n_geo : a.n_app, cc = geo ? c : c - a.n_geo, ld = geo ? args.ld_geo : args.ld_app;
+        const float *row = (geo ? args.pg_geo : args.pg_app) + (size_t)row_i * ld;
+        const float scale = c == a.blur_idx ? a.blur_scale(m, m / a.S) : 1.0f;
+        const float p = a.params_map[(size_t)m * P + c], x = c == a.blur_idx ? p * scale : p;
+        v = row[cc];
+        for (int f = 0; f < a.param_freq; ++f) {
+            v = fmaf(fourier_slope(x, f, 0), row[fourier_row_of(D, f, 0, cc)], v);
+            v = fmaf(fourier_slope(x, f, 1), row[fourier_row_of(D, f, 1, cc)], v);
+        }
+        if (c == a.blur_idx) v *= scale;
+    }
+    args.out[e] = v;
+}
 }   // namespace ntx_train
 namespace {
 using namespace ntx_train;
@@ -249,8 +307,13 @@ struct FlexBackend : Backend {
     void seg(long long &slot, size_t src, int rows, int out);
     int enable_param_gradients() override;
     void reduce(hipStream_t st, int n_split, const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out);
+    void network_forward(long long M, hipStream_t st);                      // the rows are encoded: branches, layers, heads on M rows
+    void network_backward(long long M, hipStream_t st);                     // dgrad [M][4] -> the weight gradients, the gradient at the parameter features
     int forward(const StepRays &r, hipStream_t st) override;
     int backward(const StepRays &r, hipStream_t st) override;
+    int takes_samples() override { return NTX_OK; }
+    int forward_samples(const StepSamples &s, hipStream_t st) override;
+    int backward_samples(const StepSamples &s, float *sample_pg, hipStream_t st) override;
     int activation(int layer, int64_t n_samples_total, float *out_host) override;
 };
 
@@ -411,6 +474,25 @@ int FlexBackend::forward(const StepRays &r, hipStream_t st) {
         const long long most = M * std::max(enc_Kp, enc_Kd);
         hipLaunchKernelGGL(flex_encode_kernel, dim3((unsigned)((most + 255) / 256), 2), dim3(256), 0, st, e);
     }
+    network_forward(M, st);
+    return NTX_OK;
+}
+// An instanced step: the same network on the n_live compact rows of the step's live samples (none: nothing is launched)
+int FlexBackend::forward_samples(const StepSamples &s, hipStream_t st) {
+    const long long M = s.n_live;
+    if (M == 0) return NTX_OK;
+    hipLaunchKernelGGL(flex_transpose_kernel, dim3((unsigned)((t_total + 255) / 256)), dim3(256), 0, st, t->w, wt, tseg, n_tseg, t_total);
+    FlexEncodeSamplesArgs e{}; e.s = s; e.Kp = enc_Kp; e.Kd = enc_Kd; e.n_pos_dst = n_pos_dst; e.dir = dir_dst;
+    for (int i = 0; i < n_pos_dst; ++i) e.pos[i] = pos_dst[i];
+    if (geo.exists()) e.geo_in = FlexDst{geo.in, geo.ld_in};
+    if (app.exists()) e.app_in = FlexDst{app.in, app.ld_in};
+    const long long most = M * std::max(enc_Kp, enc_Kd);
+    hipLaunchKernelGGL(flex_encode_samples_kernel, dim3((unsigned)((most + 255) / 256), 2), dim3(256), 0, st, e);
+    network_forward(M, st);
+    return NTX_OK;
+}
+void FlexBackend::network_forward(long long M, hipStream_t st) {
+    const float *W = t->w;
     if (geo.exists()) branch_forward(geo, pos_dst, n_pos_dst, M, st);        // model.py:88-93: in front of trunk layer 0
     for (size_t i = 0; i < layers.size(); ++i) {                             // a contraction per layer, every output kept
         const FlexLayer &l = layers[i];
@@ -422,7 +504,6 @@ int FlexBackend::forward(const StepRays &r, hipStream_t st) {
     const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
     hipLaunchKernelGGL(flex_head_kernel<1>, dim3(head_grid), dim3(256), 0, st, lt.Y, lt.ldy, lt.out, W + alpha.w, W + alpha.b, t->sigma, M);      // model.py:111
     hipLaunchKernelGGL(flex_head_kernel<3>, dim3(head_grid), dim3(256), 0, st, lh.Y, lh.ldy, lh.out, W + rgb.w, W + rgb.b, t->raw_rgb, M);        // :123
-    return NTX_OK;
 }
 
 // the way back from the composite's adjoint dgrad [M][4]: per layer, last to first, dW = X^T . dY over ranges of FLEX_SPLIT samples added in
@@ -475,7 +556,28 @@ void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split,
 }
 
 int FlexBackend::backward(const StepRays &r, hipStream_t st) {
-    const long long M = r.M();
+    network_backward(r.M(), st);
+    if (t->pg_mode != 0) {                                                   // the features' gradient through the encoder, a ray's samples, a row's rays
+        const int P = t->P;
+        const long long rows = (r.n_rays + r.rays_per_param_row - 1) / r.rays_per_param_row;
+        FlexFoldArgs f{}; f.r = r; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.ray_pg = ray_pg;
+        hipLaunchKernelGGL(flex_param_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
+        hipLaunchKernelGGL(flex_param_rows_kernel, dim3((unsigned)((rows * P + 255) / 256)), dim3(256), 0, st, ray_pg, r.n_rays, r.rays_per_param_row, P, rows, t->param_grad);
+    }
+    return NTX_OK;
+}
+// An instanced step's way back over its n_live rows.  Without a live sample nothing is contracted: every weight gradient is exactly 0 (mode
+// 2 leaves the buffer alone, as ever), and the per-sample parameter gradients are zeros.
+int FlexBackend::backward_samples(const StepSamples &s, float *sample_pg, hipStream_t st) {
+    if (s.n_live > 0) network_backward(s.n_live, st);
+    else if (t->pg_mode != 2) TRAIN_TRY(hipMemsetAsync(t->grad, 0, t->n_weights * sizeof(float), st));
+    if (t->pg_mode != 0) {
+        FlexSampleFoldArgs f{}; f.s = s; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.out = sample_pg;
+        hipLaunchKernelGGL(flex_param_samples_kernel, dim3((unsigned)((s.M() * t->P + 255) / 256)), dim3(256), 0, st, f);
+    }
+    return NTX_OK;
+}
+void FlexBackend::network_backward(long long M, hipStream_t st) {
     const float *W = t->w;
     const int n_split = (int)((M + FLEX_SPLIT - 1) / FLEX_SPLIT);
     auto reduce = [&](const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
@@ -530,14 +632,6 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
         launch_gemm(st, true, g);
         cur ^= 1;
     }
-    if (pgrad) {                                                             // the features' gradient through the encoder, a ray's samples, a row's rays
-        const int P = t->P;
-        const long long rows = (r.n_rays + r.rays_per_param_row - 1) / r.rays_per_param_row;
-        FlexFoldArgs f{}; f.r = r; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.ray_pg = ray_pg;
-        hipLaunchKernelGGL(flex_param_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
-        hipLaunchKernelGGL(flex_param_rows_kernel, dim3((unsigned)((rows * P + 255) / 256)), dim3(256), 0, st, ray_pg, r.n_rays, r.rays_per_param_row, P, rows, t->param_grad);
-    }
-    return NTX_OK;
 }
 
 int FlexBackend::activation(int layer, int64_t n_samples_total, float *out_host) {              // row-major buffers: a strided copy

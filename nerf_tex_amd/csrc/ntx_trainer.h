@@ -46,6 +46,18 @@ struct StepRays {
     __host__ __device__ long long M() const { return n_rays * S; }
     int n_blocks() const { return (int)((M() + 31) / 32); }       // blocks of 32 samples
 };
+// The samples of one instanced step (ntx_train_forward_instanced): the instancer's buffers as the caller handed them, and the compaction of
+// the step -- sample m = ray * S + s is LIVE iff hit[ray] != 0 && dists[m] > 0; the live samples numbered in ascending m are the rows the
+// network runs on: live[row] = m, row_of[m] = row or -1.  Nothing of pts / rays_d_map / t_map / alpha_weight / params_map is read at a
+// sample that is not live.
+struct StepSamples {
+    const float *rays_d_map, *pts, *t_map, *dists, *color_last, *alpha_last, *alpha_weight; const uint8_t *hit; const float *params_map, *cone;
+    long long n_rays; int S, blur_idx, n_geo, n_app, pos_freq, dir_freq, param_freq; float patch_scale, density_scale;
+    const int *live, *row_of; long long n_live;
+    __host__ __device__ long long M() const { return n_rays * S; }
+    // column c of a live sample's parameters as the network sees it: blur_idx's times the sample's footprint (renderer.py:259-263)
+    __device__ __forceinline__ float blur_scale(long long m, long long ray) const { return cone[ray] * t_map[m] / patch_scale; }
+};
 // The network between the encoded rays and the composite.  forward leaves sigma, raw_rgb and dists in the handle's buffers and keeps what the
 // way back needs; backward takes the handle's dgrad (and its O-layout copy dhead) to the handle's grad -- right behind the forward
 // (ntx_train_step_gradients) or later from the same StepRays (ntx_train_backward: the caller keeps the rays' buffers alive until then).
@@ -54,6 +66,15 @@ struct Backend {
     virtual int forward(const StepRays &r, hipStream_t st) = 0;
     virtual int backward(const StepRays &r, hipStream_t st) = 0;
     virtual int activation(int layer, int64_t n_samples_total, float *out_host) = 0;   // ntx_trainer_activation, the arguments checked
+    // ntx_train_forward_instanced: the network on the n_live compact rows of a StepSamples -- forward leaves sigma [n_live] and raw_rgb
+    // [n_live][3]; backward takes dgrad [n_live][4] to the handle's grad and, where asked for, the per-sample dL/d params to sample_pg [N][S][P]
+    // (takes_samples: asked before anything of the step is launched)
+    virtual int takes_samples() {
+        return ntx_set_error(NTX_E_UNSUPPORTED, "an instanced step: the fused chain (ntx_trainer_create) runs on whole rays; the layer-by-layer trainer takes the "
+                             "same model on the in-patch samples (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
+    }
+    virtual int forward_samples(const StepSamples &, hipStream_t) { return takes_samples(); }
+    virtual int backward_samples(const StepSamples &, float *, hipStream_t) { return takes_samples(); }
     // ntx_trainer_enable_param_gradients, mode 1 / 2 on a model with parameters: places what dL/d params needs (once); the handle keeps the mode
     virtual int enable_param_gradients() {
         return ntx_set_error(NTX_E_UNSUPPORTED, "parameter gradients: the fused chain (ntx_trainer_create) stops at the encoded inputs; the layer-by-layer "
@@ -81,9 +102,15 @@ struct ntx_trainer {
     int pg_mode = 0;                           // ntx_trainer_enable_param_gradients: 0 off, 1 dL/d params beside the weight gradients, 2 dL/d params alone
     float *param_grad = nullptr;               // [rows][P] of the last step (the backend places it at the first enable), pg_rows = 0: no step yet
     long long pg_rows = 0;
+    // an instanced step (ntx_train_forward_instanced), placed at the first one for the trainer's capacity: the compaction's maps and scan
+    // workspace, and -- at the first instanced backward under pg_mode 1 / 2 -- the per-sample dL/d params [N][S][P] (spg_rays = 0: no such step yet)
+    int *live = nullptr, *row_of = nullptr, *ray_live = nullptr; long long *n_live_dev = nullptr;
+    float *sample_pg = nullptr; long long spg_rays = 0; int spg_S = 0;
     long long adam_iterations = 0;
-    // ntx_train_forward's step until its ntx_train_backward: the caller's rays (alive and unchanged until then), what the composite was run with
-    struct Pending { bool open = false; ntx_train::StepRays rays{}; uint32_t flags = 0; float bkgd[3] = {1.0f, 1.0f, 1.0f}; const float *noise = nullptr; } pending;
+    // ntx_train_forward's step until its ntx_train_backward: the caller's rays (alive and unchanged until then), what the composite was run with;
+    // samples: the step is ntx_train_forward_instanced's, and smp holds the caller's buffers instead of rays
+    struct Pending { bool open = false, samples = false; ntx_train::StepRays rays{}; ntx_train::StepSamples smp{}; uint32_t flags = 0; float bkgd[3] = {1.0f, 1.0f, 1.0f};
+                     const float *noise = nullptr; } pending;
     ntx_train::Backend *backend = nullptr;
     ntx_train::DeviceMemory mem;               // (destroyed after the body below has run)
     ~ntx_trainer() { (void)hipSetDevice(device); delete backend; }

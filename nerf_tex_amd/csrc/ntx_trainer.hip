@@ -4,7 +4,9 @@
 // network: composite_loss_kernel (renderer.py:170-213 per ray, the ray's term of the loss and the adjoint of both), reduce_batch_kernel (the
 // weight gradients' partial sums added in a fixed order: a step is bit-reproducible), adam_kernel (train.py:49-52).  The same step cut in
 // two at the predictions, for a loss the caller evaluates (ntx_train_forward / ntx_train_backward): composite_forward_kernel and
-// composite_adjoint_kernel, made of the device pieces composite_loss_kernel is made of.
+// composite_adjoint_kernel, made of the device pieces composite_loss_kernel is made of.  And the same pair for the instanced render
+// (ntx_train_forward_instanced: InstanceRenderer's tail, renderer.py:247-354): the compaction of the in-patch samples (live_*_kernel),
+// inst_composite_forward_kernel and inst_composite_adjoint_kernel, the network on the compact rows.
 // The network between the encoded rays and the composite is a backend's (ntx_trainer.h): the 8 x 256 chain of ntx_backend_chain.hip behind
 // ntx_trainer_create, the layer-by-layer step of ntx_backend_flex.hip behind ntx_trainer_create_flex / _flex_ex.  Inference fuses the whole network into
 // one kernel because nothing of it has to survive (ntx_device.h); a training step has to keep every layer's activations for the weight
@@ -225,6 +227,183 @@ __global__ __launch_bounds__(256) void composite_adjoint_kernel(CompositeArgs a,
     const float dA = live && d_alpha ? d_alpha[ray] : 0.0f;
     ray_adjoint(a, ray, lane, el, T, dC, dA);
 }
+// ---------------------------------------------------------------------------------------------------------------------------
+// The instanced step (ntx_train_forward_instanced): InstanceRenderer.evaluate_model + map_model_output (renderer.py:247-354) with the
+// network on the live samples alone.  Sample m = ray * S + s is live iff hit[ray] != 0 && dists[m] > 0 (:284-288).
+// The compaction numbers the live samples in ascending m by a prefix sum in two levels and no atomic: live_count_kernel counts a ray's
+// live samples (wave per ray), live_scan_kernel turns the counts into each ray's first row (one workgroup, every thread a contiguous range
+// of rays, the threads' sums scanned in LDS) and leaves the total, live_rows_kernel numbers a ray's samples behind its first row (wave per
+// ray, a ballot per 64 samples): live[row] = m, row_of[m] = row or -1.  The order is a function of hit and dists alone.
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void live_count_kernel(const float *__restrict__ dists, const uint8_t *__restrict__ hit, long long n_rays, int S, int *__restrict__ ray_live) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    int n = 0;
+    if (hit[ray]) for (int s = lane; s < S; s += 64) n += dists[(size_t)ray * S + s] > 0.0f ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    if (lane == 0) ray_live[ray] = n;
+}
+// ray_live[r] (counts) -> the exclusive sum over the rays in front of r, in place; *n_live = the total
+__global__ __launch_bounds__(1024) void live_scan_kernel(int *__restrict__ ray_live, long long n_rays, long long *__restrict__ n_live) {
+    __shared__ int sums[1024];
+    const long long per = (n_rays + 1023) / 1024, r0 = (long long)threadIdx.x * per, r1 = r0 + per < n_rays ? r0 + per : n_rays;
+    int mine = 0;
+    for (long long r = r0; r < r1; ++r) mine += ray_live[r];
+    sums[threadIdx.x] = mine;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                                       // inclusive scan of the threads' sums
+        const int v = (int)threadIdx.x >= o ? sums[threadIdx.x - o] : 0;
+        __syncthreads();
+        sums[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int base = sums[threadIdx.x] - mine;
+    for (long long r = r0; r < r1; ++r) { const int c = ray_live[r]; ray_live[r] = base; base += c; }
+    if (threadIdx.x == 1023) *n_live = sums[1023];
+}
+__global__ __launch_bounds__(256) void live_rows_kernel(const float *__restrict__ dists, const uint8_t *__restrict__ hit, long long n_rays, int S,
+                                                        const int *__restrict__ ray_first, int *__restrict__ live, int *__restrict__ row_of) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const bool h = hit[ray] != 0;
+    int base = ray_first[ray];
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        const long long m = ray * S + s;
+        const bool lv = h && s < S && dists[m] > 0.0f;
+        const unsigned long long b = __ballot(lv);
+        const int row = base + __popcll(b & ((1ull << lane) - 1ull));
+        if (s < S) row_of[m] = lv ? row : -1;
+        if (lv) live[row] = (int)m;
+        base += __popcll(b);
+    }
+}
+// The instanced composite (renderer.py:318-354): the network's raw outputs in compact rows (sigma [n_live], raw_rgb [n_live][3]), everything else
+// in the caller's [N][S] buffers.  A live sample: sigma' = sigma * alpha_weight * density_scale (:300), a = 1 - exp(-relu(sigma') dists /
+// patch_scale) (:339).  A sample that is not live has a = 0 exactly, its factor of the running product is 1 + 1e-10.  One appended sample
+// (color_last as is, alpha_last as an alpha) closes the ray (:331, :339).  A ray with hit == 0 is 0 / 0, also under the background (:313-314).
+struct InstCompositeArgs {
+    StepSamples s; const float *raw_rgb, *sigma;
+    int map_exr, composite_bkgd; float bkgd[3];
+    float *color, *alpha;                      // [N][3], [N]
+    float *dgrad;                              // [n_live][4] in compact row order
+};
+// ray_transmittance for such a ray: el[s] = exp(-relu(sigma') dists / patch_scale), 1 where the sample is not live, and T[s]; the factors in
+// the same el + 1e-10 form (see there).  Returns the product of all S factors: the transmittance in front of the appended sample.
+__device__ __forceinline__ float inst_transmittance(const InstCompositeArgs &a, long long ray, int lane, float *el, float *T) {
+    const StepSamples &p = a.s;
+    const int S = p.S;
+    for (int s = lane; s < S; s += 64) {
+        const long long m = ray * S + s;
+        const int row = p.row_of[m];
+        float e = 1.0f;
+        if (row >= 0) {
+            const float v = a.sigma[row] * (p.alpha_weight ? p.alpha_weight[m] : 1.0f) * p.density_scale;
+            const float r = v > 0.0f ? v : 0.0f;
+            e = expf(-r * p.dists[m] / p.patch_scale);
+        }
+        el[s] = e;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float carry = 1.0f;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        float f = s < S ? el[s] + 1e-10f : 1.0f, incl = f;
+        for (int o = 1; o < 64; o <<= 1) { const float w = __shfl_up(incl, o); if (lane >= o) incl *= w; }
+        float excl = __shfl_up(incl, 1);
+        if (lane == 0) excl = 1.0f;
+        if (s < S) T[s] = carry * excl;
+        carry *= __shfl(incl, 63);
+    }
+    __builtin_amdgcn_wave_barrier();
+    return carry;
+}
+__global__ __launch_bounds__(256) void inst_composite_forward_kernel(InstCompositeArgs a) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    const StepSamples &p = a.s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long ray = (long long)blockIdx.x * 4 + wave;
+    if (ray >= p.n_rays) return;
+    if (!p.hit[ray]) { if (lane < 3) a.color[3 * ray + lane] = 0.0f; if (lane == 3) a.alpha[ray] = 0.0f; return; }
+    float *el = sh_a[wave], *T = sh_T[wave];
+    const float T_last = inst_transmittance(a, ray, lane, el, T);
+    float c[3] = {0.0f, 0.0f, 0.0f}, A = 0.0f;
+    for (int s = lane; s < p.S; s += 64) {
+        const int row = p.row_of[ray * p.S + s];
+        if (row < 0) continue;                                                                  // a = 0: no weight
+        const float w = (1.0f - el[s]) * T[s];
+        for (int k = 0; k < 3; ++k) c[k] += w * rgb_of(a.raw_rgb[3 * (size_t)row + k], a.map_exr);
+        A += w;
+    }
+    const float wl = p.alpha_last[ray] * T_last;                                                // the appended sample
+    A = wave_sumf(A) + wl;
+    for (int k = 0; k < 3; ++k) {
+        c[k] = wave_sumf(c[k]) + wl * p.color_last[3 * ray + k];
+        if (a.composite_bkgd) c[k] += (1.0f - A) * a.bkgd[k];                                   // :351-352
+    }
+    if (lane < 3) a.color[3 * ray + lane] = lane == 0 ? c[0] : lane == 1 ? c[1] : c[2];
+    if (lane == 3) a.alpha[ray] = A;
+}
+// Its adjoint from the caller's cotangents: ray_adjoint's recurrences (see there) with the appended sample behind sample S - 1, so the
+// carries start at V_{S-1} = (dC . color_last) alpha_last and Z_{S-1} = ((1 - alpha_last) + 1e-10) - 1e-10 instead of 0 and 1.  A sample
+// that is not live is the map X -> -1e-10 + (1 + 1e-10) X for Z and the identity's for V, and writes nothing.  dL/d sigma of a live sample:
+// d_a (dists / patch_scale) e alpha_weight density_scale where sigma' > 0.  A ray with hit == 0 has no live sample: nothing of it is
+// written whatever its cotangent holds, which is not even read.
+__global__ __launch_bounds__(256) void inst_composite_adjoint_kernel(InstCompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    const StepSamples &p = a.s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, S = p.S;
+    const long long ray = (long long)blockIdx.x * 4 + wave;
+    if (ray >= p.n_rays || !p.hit[ray]) return;
+    float *el = sh_a[wave], *T = sh_T[wave];
+    (void)inst_transmittance(a, ray, lane, el, T);
+    const float dC[3] = {d_color[3 * ray], d_color[3 * ray + 1], d_color[3 * ray + 2]};
+    float dA = d_alpha ? d_alpha[ray] : 0.0f;
+    if (a.composite_bkgd) dA -= (dC[0] * a.bkgd[0] + dC[1] * a.bkgd[1]) + dC[2] * a.bkgd[2];
+    const float al = p.alpha_last[ray];
+    float V_carry = ((dC[0] * p.color_last[3 * ray] + dC[1] * p.color_last[3 * ray + 1]) + dC[2] * p.color_last[3 * ray + 2]) * al;
+    float Z_carry = ((1.0f - al) + 1e-10f) - 1e-10f;
+    for (int s0 = ((S - 1) / 64) * 64; s0 >= 0; s0 -= 64) {
+        const int s = s0 + lane;
+        const long long m = ray * S + s;
+        const int row = s < S ? p.row_of[m] : -1;
+        float cs = 0.0f, rgb[3] = {0.0f, 0.0f, 0.0f}, e = 1.0f;
+        float F = 1.0f, Bz = 0.0f, Bv = 0.0f;              // the identity for the lanes past the ray's end
+        if (s < S) {
+            e = el[s];
+            if (row >= 0) {
+                for (int c = 0; c < 3; ++c) rgb[c] = rgb_of(a.raw_rgb[3 * (size_t)row + c], a.map_exr);
+                cs = (dC[0] * rgb[0] + dC[1] * rgb[1]) + dC[2] * rgb[2];
+            }
+            F = e + 1e-10f; Bz = -1e-10f; Bv = row >= 0 ? cs * (1.0f - e) : 0.0f;
+        }
+        for (int o = 1; o < 64; o <<= 1) {
+            const float Fo = __shfl_down(F, o), Bzo = __shfl_down(Bz, o), Bvo = __shfl_down(Bv, o);
+            if (lane + o < 64) { Bz = fmaf(F, Bzo, Bz); Bv = fmaf(F, Bvo, Bv); F *= Fo; }
+        }
+        float Fn = __shfl_down(F, 1), Bzn = __shfl_down(Bz, 1), Bvn = __shfl_down(Bv, 1);   // the lanes strictly behind this one
+        if (lane == 63) { Fn = 1.0f; Bzn = 0.0f; Bvn = 0.0f; }
+        const float Z = fmaf(Fn, Z_carry, Bzn), V = fmaf(Fn, V_carry, Bvn);
+        if (row >= 0) {
+            const float w = (1.0f - e) * T[s];
+            const float d_a = T[s] * fmaf(dA, Z, cs - V);
+            const float aw = p.alpha_weight ? p.alpha_weight[m] : 1.0f;
+            const float sig = a.sigma[row] * aw * p.density_scale;
+            float gr[4];
+            for (int c = 0; c < 3; ++c) {
+                const float raw = a.raw_rgb[3 * (size_t)row + c];
+                const float drgb = a.map_exr ? (raw > 0.0f ? 1.0f : expf(raw)) : rgb[c] * (1.0f - rgb[c]);
+                gr[c] = w * dC[c] * drgb;
+            }
+            gr[3] = sig > 0.0f ? d_a * (p.dists[m] / p.patch_scale) * e * aw * p.density_scale : 0.0f;
+            *reinterpret_cast<f32x4 *>(a.dgrad + 4 * (size_t)row) = f32x4{gr[0], gr[1], gr[2], gr[3]};
+        }
+        const float F0 = __shfl(F, 0);
+        Z_carry = fmaf(F0, Z_carry, __shfl(Bz, 0)); V_carry = fmaf(F0, V_carry, __shfl(Bv, 0));
+    }
+}
 // the loss: the rays' terms added up by one workgroup in a fixed order
 __global__ __launch_bounds__(1024) void loss_sum_kernel(const float *__restrict__ ray_loss, int n_rays, float *__restrict__ loss) {
     __shared__ float red[1024];
@@ -421,6 +600,27 @@ static CompositeArgs composite_args(const ntx_trainer *t, const StepRays &rays, 
     return c;
 }
 
+// ... of an instanced step, and its second half: the adjoint over the pending samples, the backend's way back over the compact rows and --
+// under ntx_trainer_enable_param_gradients -- the per-sample dL/d params (placed at the first such step, for the capacity)
+static InstCompositeArgs inst_composite_args(const ntx_trainer *t, const StepSamples &s, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred) {
+    InstCompositeArgs c{};
+    c.s = s; c.raw_rgb = t->raw_rgb; c.sigma = t->sigma; c.map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0; c.composite_bkgd = (flags & NTX_FLAG_COMPOSITE_BKGD) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) c.bkgd[k] = bkgd ? bkgd[k] : 1.0f;
+    c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.dgrad = t->dgrad;
+    return c;
+}
+static int backward_instanced(ntx_trainer *t, const float *d_color, const float *d_alpha, hipStream_t st) {
+    const StepSamples &s = t->pending.smp;
+    if (t->pg_mode != 0 && !t->sample_pg && t->mem.alloc(&t->sample_pg, (size_t)t->cap * t->P) != NTX_OK) return t->mem.rc;
+    const InstCompositeArgs c = inst_composite_args(t, s, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
+    if (s.n_live > 0) hipLaunchKernelGGL(inst_composite_adjoint_kernel, dim3((unsigned)((s.n_rays + 3) / 4)), dim3(256), 0, st, c, d_color, d_alpha);
+    int rc = t->backend->backward_samples(s, t->sample_pg, st);
+    if (rc != NTX_OK) return rc;
+    TRAIN_TRY(hipGetLastError());
+    if (t->pg_mode != 0) { t->spg_rays = s.n_rays; t->spg_S = s.S; t->pg_rows = 0; }
+    return NTX_OK;
+}
+
 int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *rays_d, const float *tnear_far, const float *params, int64_t rays_per_param_row,
                              const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
                              const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,
@@ -447,7 +647,7 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
     rc = t->backend->backward(rays, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
-    if (t->pg_mode != 0) t->pg_rows = (n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row;
+    if (t->pg_mode != 0) { t->pg_rows = (n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row; t->spg_rays = 0; }
     return NTX_OK;
 }
 
@@ -464,7 +664,7 @@ int ntx_train_forward(ntx_trainer *t, const float *rays_o, const float *rays_d, 
     const CompositeArgs c = composite_args(t, rays, noise, flags, bkgd, color_pred, alpha_pred);
     hipLaunchKernelGGL(composite_forward_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c);
     TRAIN_TRY(hipGetLastError());
-    t->pending.rays = rays; t->pending.flags = flags; t->pending.noise = noise;
+    t->pending.rays = rays; t->pending.flags = flags; t->pending.noise = noise; t->pending.samples = false;
     for (int k = 0; k < 3; ++k) t->pending.bkgd[k] = c.bkgd[k];
     t->pending.open = true;
     return NTX_OK;
@@ -476,6 +676,7 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
     if (!d_color) return ntx_set_error(NTX_E_INVALID, "d_color is NULL");
     t->pending.open = false;
     TRAIN_TRY(hipSetDevice(t->device));
+    if (t->pending.samples) return backward_instanced(t, d_color, d_alpha, (hipStream_t)stream);
     const StepRays &rays = t->pending.rays;
     CompositeArgs c = composite_args(t, rays, t->pending.noise, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
     c.weights = nullptr;                                                                        // (b) alone: nothing of the forward is written again
@@ -483,7 +684,59 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
     int rc = t->backend->backward(rays, (hipStream_t)stream);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
-    if (t->pg_mode != 0) t->pg_rows = (rays.n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row;
+    if (t->pg_mode != 0) { t->pg_rows = (rays.n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row; t->spg_rays = 0; }
+    return NTX_OK;
+}
+
+int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const float *pts, const float *t_map, const float *dists, const float *color_last,
+                                const float *alpha_last, const float *alpha_weight, const uint8_t *hit, const float *params_map, const float *cone_scale, int64_t n_rays,
+                                int n_samples, int blur_idx, float patch_scale, float density_scale, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred,
+                                int64_t *n_live_out, ntx_stream stream) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    t->pending.open = false;                                                                    // a new forward of either kind replaces the one left open
+    if (int rc = t->backend->takes_samples()) return rc;
+    if (!rays_d_map || !pts || !dists || !color_last || !alpha_last || !hit || (t->P > 0 && !params_map)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (n_samples < 1 || n_samples > MAX_TRAIN_SAMPLES) return ntx_set_error(NTX_E_INVALID, "n_samples outside 1 .. %d", MAX_TRAIN_SAMPLES);
+    if (n_rays < 1 || n_rays > t->cap_rays || (long long)n_rays * n_samples > t->cap) return ntx_set_error(NTX_E_INVALID, "n_rays x n_samples beyond what the trainer was created for");
+    if (!(patch_scale > 0.0f)) return ntx_set_error(NTX_E_INVALID, "patch_scale must be > 0");
+    if (blur_idx >= t->P || (blur_idx >= 0 && (!cone_scale || !t_map))) return ntx_set_error(NTX_E_INVALID, "bad blur_idx / cone_scale / t_map");
+    if (flags & (NTX_FLAG_PERTURB | NTX_FLAG_RAW_NOISE))
+        return ntx_set_error(NTX_E_INVALID, "NTX_FLAG_PERTURB / NTX_FLAG_RAW_NOISE: the instancer places the samples, and the density noise of an instanced step is not built");
+    hipStream_t st = (hipStream_t)stream;
+    TRAIN_TRY(hipSetDevice(t->device));
+    if (!t->live) {                                                                             // the first instanced step places its maps, for the capacity
+        DeviceMemory &mem = t->mem;
+        mem.alloc(&t->live, (size_t)t->cap); mem.alloc(&t->row_of, (size_t)t->cap); mem.alloc(&t->ray_live, (size_t)t->cap_rays); mem.alloc(&t->n_live_dev, 1);
+        if (mem.rc != NTX_OK) return mem.rc;
+    }
+    const unsigned ray_grid = (unsigned)((n_rays + 3) / 4);
+    hipLaunchKernelGGL(live_count_kernel, dim3(ray_grid), dim3(256), 0, st, dists, hit, (long long)n_rays, n_samples, t->ray_live);
+    hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, t->ray_live, (long long)n_rays, t->n_live_dev);
+    hipLaunchKernelGGL(live_rows_kernel, dim3(ray_grid), dim3(256), 0, st, dists, hit, (long long)n_rays, n_samples, t->ray_live, t->live, t->row_of);
+    long long n_live = 0;                                                                       // the launches are sized on the host: the step's one synchronisation
+    TRAIN_TRY(hipMemcpyAsync(&n_live, t->n_live_dev, sizeof(n_live), hipMemcpyDeviceToHost, st));
+    TRAIN_TRY(hipStreamSynchronize(st));
+    if (n_live < 0 || n_live > (long long)n_rays * n_samples) return ntx_set_error(NTX_E_HIP, "the compaction counted %lld live samples of %lld", n_live, (long long)n_rays * n_samples);
+    if (n_live_out) *n_live_out = n_live;
+    const ntx_model_desc &d = t->desc;
+    StepSamples s{rays_d_map, pts, t_map, dists, color_last, alpha_last, alpha_weight, hit, params_map, cone_scale, n_rays, n_samples, blur_idx, d.n_geo, d.n_app, d.pos_freq,
+                  d.dir_freq, d.param_freq, patch_scale, density_scale, t->live, t->row_of, n_live};
+    int rc = t->backend->forward_samples(s, st);
+    if (rc != NTX_OK) return rc;
+    const InstCompositeArgs c = inst_composite_args(t, s, flags, bkgd, color_pred, alpha_pred);
+    hipLaunchKernelGGL(inst_composite_forward_kernel, dim3(ray_grid), dim3(256), 0, st, c);
+    TRAIN_TRY(hipGetLastError());
+    t->pending.smp = s; t->pending.flags = flags; t->pending.noise = nullptr; t->pending.samples = true;
+    for (int k = 0; k < 3; ++k) t->pending.bkgd[k] = c.bkgd[k];
+    t->pending.open = true;
+    return NTX_OK;
+}
+
+int ntx_trainer_sample_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *n_rays, int *n_samples, int *n_params) {
+    if (!t || !grad_dev || !n_rays || !n_samples || !n_params) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (t->pg_mode == 0 || t->spg_rays == 0) return ntx_set_error(NTX_E_INVALID, "no per-sample parameter gradients: %s", t->pg_mode == 0 ? "ntx_trainer_enable_param_gradients is off" :
+                                                                  "the last step since they were enabled was not an instanced one (ntx_trainer_param_gradients has a plain step's)");
+    *grad_dev = t->sample_pg; *n_rays = t->spg_rays; *n_samples = t->spg_S; *n_params = t->P;
     return NTX_OK;
 }
 
@@ -492,7 +745,7 @@ int ntx_trainer_enable_param_gradients(ntx_trainer *t, int mode) {
     if (mode != 0) {
         int rc = t->backend->enable_param_gradients();                                          // the chain refuses; the layer-by-layer backend places its buffers once
         if (rc != NTX_OK) return rc;
-    } else t->pg_rows = 0;
+    } else { t->pg_rows = 0; t->spg_rays = 0; }
     t->pg_mode = mode;
     return NTX_OK;
 }
@@ -500,7 +753,8 @@ int ntx_trainer_enable_param_gradients(ntx_trainer *t, int mode) {
 int ntx_trainer_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *rows, int *n_params) {
     if (!t || !grad_dev || !rows || !n_params) return ntx_set_error(NTX_E_INVALID, "NULL argument");
     if (t->pg_mode == 0 || t->pg_rows == 0) return ntx_set_error(NTX_E_INVALID, "no parameter gradients: %s", t->pg_mode == 0 ? "ntx_trainer_enable_param_gradients is off" :
-                                                                 "no step has run since they were enabled");
+                                                                 (t->spg_rays ? "the last step was an instanced one (ntx_trainer_sample_param_gradients has its per-sample gradients)" :
+                                                                  "no step has run since they were enabled"));
     *grad_dev = t->param_grad; *rows = t->pg_rows; *n_params = t->P;
     return NTX_OK;
 }

@@ -20,7 +20,8 @@ contraction per Dense layer and pass (`ntx_trainer_create_flex`); `BranchTrainer
 gradient a training step otherwise leaves out, dL/d material parameters (`param_gradients=`, `parameter_gradients()`); `nerf_tex_amd.fit`
 fits parameters to target images with it.  The losses of `nerf_tex_amd.loss` are evaluated inside the step; any other loss is a callable on
 torch tensors, and the step runs as `forward(...)`, the loss and its two cotangents in torch, `backward(d_color, d_alpha)`
-(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op)."""
+(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op).  The layer-by-layer trainers also take the step through
+the INSTANCED render (`forward_instanced(bufs, ...)` on an instancer's buffers, then the same `backward`; `DifferentiableInstanceRender`)."""
 
 from __future__ import annotations
 
@@ -417,6 +418,62 @@ class FlexTrainer(Trainer):
         _lib.check(_lib.lib.ntx_trainer_param_gradients(self._h, C.byref(ptr), C.byref(rows), C.byref(n)))
         dev = torch.device("cuda", self.device)
         out = torch.empty((int(rows.value), int(n.value)), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def forward_instanced(self, bufs, cone_scale, *, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True, composite_bkgd: bool = False,
+                          bkgd_color=(1., 1., 1.), hit=None):
+        """The first half of a step on the INSTANCED render (`ntx_train_forward_instanced`): InstanceRenderer's tail (renderer.py:247-354) with
+        every activation kept, the network on the in-patch samples alone.  `bufs`: the ten-tuple of an instancer's `get_model_input` --
+        rays_d_map [N,S,3], pts [N,S,3], t [N,S], dists [N,S], color_last [N,1,3], alpha_last [N,1], alpha_weight [N,S], instance_id (unused),
+        idxs (indices of the hit rays [k,1] or a bool mask [N]), params_map [N,S,P] -- as numpy arrays or tensors; `hit` [N] (the native
+        instancer's `last_hit`) takes the place of idxs.  `cone_scale` [N] (read with blur_idx only).  Returns (color_pred [N,3], alpha_pred
+        [N]) as GPU tensors and leaves the step pending until `backward(d_color, d_alpha)`, exactly as `forward` does; `self.last_live` is
+        the number of in-patch samples the network ran on (reading it back is the step's one synchronisation).  Float32, contiguous device
+        tensors are read in place and must not be written before the backward."""
+        import numpy as np
+        import torch
+        dev, to, ptr = self._device_tools()
+        self._pending = None
+        rays_d_map, pts, tt, dists, color_last, alpha_last, alpha_weight, _, idxs, params_map = bufs
+        dists = to(dists)
+        n, S = int(dists.shape[0]), int(dists.shape[1])
+        if hit is None:
+            idxs = idxs.detach().cpu().numpy() if isinstance(idxs, torch.Tensor) else np.asarray(idxs)
+            mask = np.zeros(n, np.uint8)
+            mask[idxs.reshape(-1) if idxs.dtype == np.bool_ else idxs.reshape(-1).astype(np.int64)] = 1
+            hit = mask
+        hit = (hit if isinstance(hit, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(hit))).to(device=dev).ne(0).to(torch.uint8).contiguous()
+        P = int(getattr(self.model, "n_params", 0))
+        keep = dict(rd=to(rays_d_map), pts=to(pts), t=to(tt), dists=dists, cl=to(color_last), al=to(alpha_last), aw=to(alpha_weight) if density_reweighting else None, hit=hit,
+                    pm=to(params_map) if P > 0 else None, cone=to(cone_scale))
+        sizes = dict(rd=3 * n * S, pts=3 * n * S, t=n * S, cl=3 * n, al=n, aw=n * S, hit=n, pm=n * S * P, cone=n)
+        for k, want in sizes.items():
+            if keep[k] is not None and keep[k].numel() != want:
+                raise ValueError(f"forward_instanced: buffer '{k}' holds {keep[k].numel()} elements, {n} rays x {S} samples need {want}")
+        flags = (_lib.FLAG_MAP_EXR if self.map_exr else 0) | (_lib.FLAG_COMPOSITE_BKGD if composite_bkgd else 0)
+        color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev)
+        live = C.c_int64(0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.ntx_train_forward_instanced(
+                self._h, ptr(keep["rd"]), ptr(keep["pts"]), ptr(keep["t"]), ptr(dists), ptr(keep["cl"]), ptr(keep["al"]), ptr(keep["aw"]), ptr(hit), ptr(keep["pm"]),
+                ptr(keep["cone"]), n, S, -1 if self.blur_idx is None else int(self.blur_idx), float(patch_scale), float(density_scale), flags, _lib.f3(bkgd_color),
+                ptr(color), ptr(alpha), C.byref(live), torch.cuda.current_stream(dev).cuda_stream))
+        self.last_live = int(live.value)
+        self._last_rays = n
+        self._forwards += 1
+        self._pending = (self._forwards, n, keep)
+        return color, alpha
+
+    def sample_parameter_gradients(self):
+        """dL/d params_map of the last INSTANCED step: a torch tensor [N, S, P] on the trainer's device (geometry columns first, exact zeros at
+        samples outside every patch), a copy in the current stream's order."""
+        import torch
+        ptr, n, s, p = C.c_void_p(), C.c_int64(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib.ntx_trainer_sample_param_gradients(self._h, C.byref(ptr), C.byref(n), C.byref(s), C.byref(p)))
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((int(n.value), int(s.value), int(p.value)), device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
         return out
