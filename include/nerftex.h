@@ -575,6 +575,17 @@ int ntx_trainer_device_weights(ntx_trainer *t, const float **weights_dev);
  * C[M][N] = op(A) . op(B) (+ bias[N]) (ReLU); a_kcontig: A is [M][K] (row stride lda), else [K][M]; B is [K][N] (b_kcontig must be 0). */
 int ntx_gemm_f32(const float *A, int lda, int a_kcontig, const float *B, int ldb, int b_kcontig, float *C, int ldc, int M, int N, int K, const float *bias,
                  int relu, ntx_stream stream);
+/* The same contraction with the launcher's whole argument list (ABI v7, appended), for tests and benches of the kernel itself: what the
+ * layer-by-layer training step passes it, on DEVICE buffers.  A, lda, a_kcontig, B [K][N], ldb, C, ldc, M, N, K, bias, relu as above.  The
+ * epilogue, in this order: C[i][j] = acc (+ the C[i][j] found there, with accumulate) + bias[j]; ReLU; then, with mask (row stride ldmask),
+ * 0 wherever !(mask[i][j] > 0).  n_split > 1 cuts K into ranges of k_chunk: range z covers p in [z k_chunk, min((z + 1) k_chunk, K)) and
+ * writes its own product (epilogue included) to C + z split_stride; n_split = 1 is the whole of K, and k_chunk and split_stride are not
+ * looked at.  colsum (NULL, or [n_split][N]; only with a_kcontig = 0, the weight-gradient form): colsum[z][j] = the sum of B[p][j] over range
+ * z, in a fixed order.  NTX_E_INVALID, before anything is launched or written: a NULL A, B or C; M, N or K < 1; lda < K (a_kcontig) or < M,
+ * ldb < N, ldc < N, mask with ldmask < N; n_split outside 1 .. 65535; with n_split > 1, k_chunk < 1, K outside ((n_split - 1) k_chunk,
+ * n_split k_chunk] or split_stride < (M - 1) ldc + N; colsum with a_kcontig != 0. */
+int ntx_gemm_f32_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
+                    const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum, ntx_stream stream);
 /* A trainer for any architecture the flex render family takes (ABI v7, appended): kind NTX_MODEL_NERF or NTX_MODEL_PARAMNERF, NTX_POS_FOURIER
  * on n_pos 3, depth 1..24, width 2..256, color_depth 0..4 (0 for a Nerf), skip = one index or NTX_SKIP_MASK | bits with every index below
  * depth - 1, n_geo <= 4, n_app <= 8, n_freq_bands <= 10 / 4 / 4 -- the 8 x 256 / skips [4] / color_depth 1 shape of ntx_trainer_create

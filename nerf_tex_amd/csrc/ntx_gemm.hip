@@ -1,5 +1,5 @@
 // ntx_gemm.hip -- the general f32 contraction on the matrix cores: one Dense layer and pass of the layer-by-layer training step
-// (ntx_backend_flex.hip) and ntx_gemm_f32 on caller buffers, all through one launcher.  Since it cuts the rows into launches of at most
+// (ntx_backend_flex.hip) and ntx_gemm_f32 / ntx_gemm_f32_ex on caller buffers, all through one launcher.  Since it cuts the rows into launches of at most
 // 65 535 tiles, ntx_gemm_f32 also takes an M beyond 65 535 x 128 rows, which used to fail at launch.  gfx950 only.
 //   C[i][j] = sum_p A'(i, p) B(p, j) for i < M, j < N, p < K, with B[p * ldb + j] and
 //   A'(i, p) = A_KCONTIG ? A[i * lda + p] : A[p * lda + i]
@@ -212,6 +212,7 @@ __global__ __launch_bounds__(TN_ * 2) __attribute__((amdgpu_waves_per_eu(WAVES_P
 void launch_gemm(hipStream_t st, bool a_kcontig, GemmArgs g, int n_split) {
     if (n_split == 1) g.k_chunk = g.K;
     g.aligned = (g.lda % 4 == 0) && (g.ldb % 4 == 0) && (((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0);
+    if (a_kcontig && n_split > 1 && g.k_chunk % 4 != 0) g.aligned = 0;      // range z starts z * k_chunk floats into A's rows (the dW form starts at whole rows)
     const long long rows_max = 65535LL * TM, M = g.M;
     for (long long r0 = 0; r0 < M; r0 += rows_max) {
         GemmArgs h = g;
@@ -232,6 +233,26 @@ extern "C" int ntx_gemm_f32(const float *A, int lda, int a_kcontig, const float 
     ntx_train::GemmArgs g{}; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
     if (b_kcontig) return ntx_set_error(NTX_E_UNSUPPORTED, "B must be [K][N]");
     ntx_train::launch_gemm((hipStream_t)stream, a_kcontig != 0, g);
+    TRAIN_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+/* The launcher's whole argument list on caller buffers (DEVICE): every field of GemmArgs and the K split, see include/nerftex.h.  Every
+ * refusal comes before the first launch.  For tests and benches of the kernel itself. */
+extern "C" int ntx_gemm_f32_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
+                               const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum, ntx_stream stream) {
+    if (!A || !B || !C || M < 1 || N < 1 || K < 1) return ntx_set_error(NTX_E_INVALID, "bad GEMM arguments");
+    if (lda < (a_kcontig ? K : M) || ldb < N || ldc < N || (mask && ldmask < N)) return ntx_set_error(NTX_E_INVALID, "a leading dimension is smaller than its row");
+    if (n_split < 1 || n_split > 65535) return ntx_set_error(NTX_E_INVALID, "n_split must be 1 .. 65535");
+    if (n_split > 1) {
+        if (k_chunk < 1 || (long long)K <= (long long)(n_split - 1) * k_chunk || (long long)K > (long long)n_split * k_chunk)
+            return ntx_set_error(NTX_E_INVALID, "K must end inside the last of n_split ranges of k_chunk");
+        if ((long long)split_stride < (long long)(M - 1) * ldc + N) return ntx_set_error(NTX_E_INVALID, "split_stride is shorter than one result");
+    }
+    if (colsum && a_kcontig) return ntx_set_error(NTX_E_INVALID, "column sums are taken in the form A [K][M] only");
+    ntx_train::GemmArgs g{}; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
+    g.mask = mask; g.ldmask = ldmask; g.accumulate = accumulate; g.k_chunk = k_chunk; g.split_stride = n_split > 1 ? (long long)split_stride : 0; g.colsum = colsum;
+    ntx_train::launch_gemm((hipStream_t)stream, a_kcontig != 0, g, n_split);
     TRAIN_TRY(hipGetLastError());
     return NTX_OK;
 }

@@ -55,10 +55,12 @@ def test_gradients_of_every_layer_match_float64_autograd(arch_id, npar, kind, ar
     one_step(model, spec, wts, fam, 45, 37, **KNOBS[arch_id])
 
 
-@pytest.mark.parametrize("n,S", [(300, 70), (41, 70)])
+@pytest.mark.parametrize("n,S", [(300, 70), (41, 70), (239, 64), (500, 64)])
 def test_the_weight_gradients_split(n, S):
     """dW = X^T . dY is summed over ranges of 2048 samples (FLEX_SPLIT in csrc/ntx_backend_flex.hip), the ranges added in ascending order: 21 000 samples
-    are ten whole ranges and one of 520, 2870 samples one whole range and one of 822.  70 samples a ray also cross the composite's 64-sample chunk."""
+    are ten whole ranges and one of 520, 2870 samples one whole range and one of 822.  70 samples a ray also cross the composite's 64-sample chunk.
+    15 296 samples are 8 ranges (the last of 960) and 32 000 are 16 (the last of 1280): a multiple of 8 ranges, as every real batch has, takes the
+    contraction's XCD-major tile numbering (gemm_place in csrc/ntx_gemm.hip)."""
     model, spec, wts = make_model((1, 6), dense_media=True, arch=dict(width=64, depth=3))
     assert (n * S) % 2048 not in (0, 1024) and n * S > 2048
     one_step(model, spec, wts, "carpet", n, S, "alpha_smape", perturb=True)

@@ -2,7 +2,8 @@
 one `gradients_step`, then of the weights and both Adam moments after two more whole steps.  The cases are the smallest seeded batches that
 reach every path of the native training code (both backends, every forward-chain build, both encoders, the per-ray direction row, the
 2048-sample split, the composite weights of a coarse pass, the contraction alone; behind them the parameter branches of
-ntx_trainer_create_flex_ex, which a library without that entry cannot run: compare the lines in front of them).  A step is bit-reproducible, so two runs on one library
+ntx_trainer_create_flex_ex, which a library without that entry cannot run: compare the lines in front of them; last, a step of eight ranges of
+the split, whose weight gradients take the contraction's XCD-major tile numbering).  A step is bit-reproducible, so two runs on one library
 print the same lines, and a change that only moves code prints what its parent prints:
     NERFTEX_LIB=<parent's libnerftex_hip.so> python tools/train_fingerprint.py > parent.jsonl
     python tools/train_fingerprint.py > new.jsonl && cmp parent.jsonl new.jsonl
@@ -93,6 +94,14 @@ def branches(npar, arch, fam, n=45, S=37, **kw):
     return fingerprint(tr, (ro, rd, t, params, cone, color, alpha), make_loss("alpha_smape")[1])
 
 
+def flex_ranges(n, S):
+    """The 3 x 64 model of tests/test_gpu_train_flex.py::test_the_weight_gradients_split on n x S samples"""
+    from nerf_tex_amd.train import FlexTrainer
+    model, _, _ = make_model((1, 6), dense_media=True, arch=dict(width=64, depth=3))
+    tr = FlexTrainer(model, max_rays=n, n_samples=S, perturb=True)
+    return fingerprint(tr, family_batch("carpet", n, S, 7), make_loss("alpha_smape")[1])
+
+
 def coarse_fine():
     from nerf_tex_amd.train import CoarseFineTrainer, FlexTrainer
     n = 16
@@ -144,6 +153,8 @@ CASES = [
     ("branches both (4,8) d6 w200 [0,4] cd2 pd4 pw100", lambda: branches((4, 8), dict(depth=6, width=200, skips=[0, 4], color_depth=2, param_depth=4, param_width=100), "carpet")),
     ("branches (2,3) d4 w128 [1,2] cd0 pd3 pw64 41x70 blur0 noise", lambda: branches((2, 3), dict(depth=4, width=128, skips=[1, 2], color_depth=0, param_depth=3, param_width=64),
                                                                                  "grass_filtered", 41, 70, blur_idx=0, raw_noise_std=0.1)),     # the branch input differs per sample
+    # appended last, so that the lines above still compare with an earlier library's
+    ("flex 3x64 carpet 239x64: eight ranges of the 2048-sample split", lambda: flex_ranges(239, 64)),                     # 15 296 samples: the XCD-major tile numbering of a weight gradient
 ]
 SAME_AS = (", extended descriptor", ", ntx_trainer_create_flex_ex")               # a case named "<other case><suffix>" has to print that case's hashes
 
