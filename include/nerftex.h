@@ -630,7 +630,8 @@ int ntx_trainer_create_flex_ex(const ntx_model_desc_ex *desc, const float *weigh
  * What is differentiated: the parameter rows `params` of the step, through FourierFeatures(parameters) (identity, sin and cos rows of every
  * band, at the value the encoder fed) and, for blur_idx, through its product with the sample's cone_scale * z (renderer.py:155-158), into
  * every layer that reads the parameter features: trunk layer 0 and the layers behind a skip (geometry), the first layer that reads dir_map
- * (appearance) -- or the first layer of each parameter branch when param_depth > 0.  Positions and directions take no gradient.
+ * (appearance) -- or the first layer of each parameter branch when param_depth > 0.  Positions and directions take theirs under
+ * ntx_trainer_enable_input_gradients.
  * The order of the sums: the readers' terms in descending layer order; the samples of a ray in a fixed order of the ray's own (64 interleaved
  * partial sums, then a butterfly); the rays of a parameter row r / rays_per_param_row in ascending ray order.  None depends on the
  * trainer's capacity or on a launch's grid: a step's parameter gradients are bit-reproducible.  A ray with tnear_far = inf contributes
@@ -686,8 +687,8 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
  * ntx_train_backward(t, d_color, d_alpha, stream) -- one backward per forward; a new forward of either kind or an ntx_train_step_gradients
  * replaces a pending one; a NULL d_color leaves it pending.  The backward: ray_adjoint's recurrences with the appended sample behind sample
  * S - 1 (the carries start at V = (dC . color_last) alpha_last, Z = ((1 - alpha_last) + 1e-10) - 1e-10); dL/d sigma of a live sample =
- * d_a * (dists / patch_scale) * e * alpha_weight * density_scale where sigma' > 0; color_last, alpha_last, alpha_weight, positions and
- * directions take no gradient.
+ * d_a * (dists / patch_scale) * e * alpha_weight * density_scale where sigma' > 0; color_last, alpha_last and alpha_weight take no gradient;
+ * positions and directions take theirs under ntx_trainer_enable_input_gradients (ntx_trainer_sample_input_gradients).
  * dL/d params (ntx_trainer_enable_param_gradients mode 1 / 2, semantics unchanged): an instanced step leaves PER-SAMPLE gradients
  * grad_dev[N][S][P] (geometry columns first; through FourierFeatures and, for blur_idx, times cone_scale * t / patch_scale; exact zeros at
  * samples that are not live) behind ntx_trainer_sample_param_gradients (DEVICE memory of the trainer, valid until the next step;
@@ -701,6 +702,42 @@ int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const f
                                 float patch_scale, float density_scale, uint32_t flags, const float *bkgd, float *color_pred,
                                 float *alpha_pred, int64_t *n_live_out, ntx_stream stream);
 int ntx_trainer_sample_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *n_rays, int *n_samples, int *n_params);
+/* dL/d rays and sample points (ABI v7, appended): the third kind of input of the layer-by-layer step -- where the rays and the sample points
+ * are -- for camera or pose refinement against photographs (plain step) and for deforming or placing the volume a texture lives in (instanced
+ * step).  For a handle of ntx_trainer_create_flex / ntx_trainer_create_flex_ex, any model they take (a Nerf included).
+ * mode 0: off (the default; nothing about the handle, its allocations, its launches or its results changes).  mode 1: every following
+ * ntx_train_step_gradients, ntx_train_forward + ntx_train_backward and ntx_train_forward_instanced + ntx_train_backward also leaves the input
+ * gradients; loss, predictions, weight gradients and parameter gradients stay bit for bit what they are without it.  mode 2: inputs with fixed
+ * weights (pose fitting) -- no weight gradient is contracted or reduced and the trainer's gradient buffer is left untouched: the weight
+ * gradient is taken unless EITHER this mode or ntx_trainer_enable_param_gradients' is 2, and ntx_trainer_adam_step,
+ * ntx_trainer_allreduce_gradients and ntx_trainer_stash_gradients return NTX_E_INVALID while either is.  Buffers are placed at the first
+ * enable, for the trainer's capacity; the transposed weight rows it needs go behind the ones already placed.  A change of the mode drops a
+ * pending ntx_train_forward (its ntx_train_backward returns NTX_E_INVALID): set the mode before the forward.
+ * NTX_E_UNSUPPORTED: a handle of ntx_trainer_create.  NTX_E_INVALID: a mode outside 0..2.
+ * What is differentiated: rays_o and rays_d of a plain step, pts and rays_d_map of an instanced one.  The sample depths are constants:
+ * tnear_far, z_vals, the jitter and sample_pdf take no gradient (renderer.py:129), nor does cone_scale; the blur product cone_scale * z (plain)
+ * or cone_scale * t / patch_scale (instanced) does not depend on the ray.  With K3p = 3 (1 + 2 pos_freq) and K3d = 3 (1 + 2 dir_freq): every
+ * trunk layer that reads pos_map (layer 0 and the layers behind a skip, with or without parameter branches) contributes dY . W[first K3p
+ * rows]^T to the gradient at the FF(xyz) rows of a sample, the first layer that reads dir_map (index depth + 1: the colour half layer when
+ * color_depth = 0) dY . W[first K3d rows]^T at the FF(dir) rows; the readers' terms are added in descending layer order.  Through the encoder a
+ * row becomes a 3-vector: component c is the identity row plus, per band, slope(sin row) + slope(cos row) at the value x_c the encoder fed --
+ * a_s for the position of sample s, b_s for its direction.
+ * A plain step, a ray with depths z_s, n = d / |d|, B = sum_s b_s:
+ *     d_rays_o = sum_s a_s,     d_rays_d = sum_s z_s a_s + (B - n (n . B)) / |d| + n dL/d|d|
+ * where dL/d|d| = (sum_s dL/d sigma_s (sigma_s + noise_s)) / |d| is the composite's dists = dz |d| (renderer.py:180).  The samples of a ray are
+ * added in a fixed order of the ray's own (64 interleaved partial sums, then a butterfly): bit-reproducible, independent of the trainer's
+ * capacity.  A ray with tnear_far = inf gets exactly 0 in both rows whatever its cone_scale and cotangent hold (NaN and inf included).
+ * An instanced step: d_pts[m] = a and d_dirs[m] = b of live sample m (the direction is fed as given: no normalisation term; dists are the
+ * caller's: no |d| term), exact zeros at samples that are not live, where nothing of pts / rays_d_map is read; n_live = 0: both are zeros.
+ * Out of scope: depths and tnear_far, cone_scale, the chain, a coarse + fine pair (two steps: add the two results), color_last / alpha_last /
+ * alpha_weight, second order. */
+int ntx_trainer_enable_input_gradients(ntx_trainer *t, int mode);
+/* Where the last PLAIN step left them: d_rays_o[n_rays][3] and d_rays_d[n_rays][3], DEVICE memory of the trainer, written in the step's
+ * stream order, valid until the next step.  NTX_E_INVALID in mode 0, before any step since the enable, or after an instanced step. */
+int ntx_trainer_ray_gradients(ntx_trainer *t, const float **d_rays_o, const float **d_rays_d, int64_t *n_rays);
+/* Where the last INSTANCED step left them: d_pts[n_rays][n_samples][3] and d_dirs[n_rays][n_samples][3] (dL/d rays_d_map), as above.
+ * NTX_E_INVALID in mode 0, or when the last step since the enable was not an instanced one. */
+int ntx_trainer_sample_input_gradients(ntx_trainer *t, const float **d_pts, const float **d_dirs, int64_t *n_rays, int *n_samples);
 
 #ifdef __cplusplus
 }

@@ -168,6 +168,9 @@ SYMBOLS = {
     "ntx_train_backward": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ntx_train_forward_instanced": (C.c_int, [_vp] * 11 + [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32, _fp, _vp, _vp, _i64p, _vp]),
     "ntx_trainer_sample_param_gradients": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ntx_trainer_enable_input_gradients": (C.c_int, [_vp, C.c_int]),
+    "ntx_trainer_ray_gradients": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64)]),
+    "ntx_trainer_sample_input_gradients": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
 }
 
 

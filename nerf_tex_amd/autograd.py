@@ -11,6 +11,10 @@ Every gradient of a step is linear in dL/d color_pred and dL/d alpha_pred, so au
 (`gradients()`, `sync_gradients`, `apply_gradients`), and -- with `param_gradients=True` / "only" on a layer-by-layer trainer and
 `parameters.requires_grad` -- dL/d parameters flows on into `parameters.grad` [rows, P], where other torch terms on `parameters` add up.
 
+With `input_gradients=True` / "only" on a layer-by-layer trainer, `rays_o` / `rays_d` that require grad receive dL/d rays_o and dL/d rays_d
+likewise (camera or pose refinement: the sample depths are constants), and the instanced op's `pts` / `rays_d_map` theirs; with it off, both ops
+do what they do without it.
+
 One backward per forward (the activations are the trainer's, not the graph's), first order only: nothing differentiates the backward.  A
 data-parallel mean of the ranks' gradients is the gradient of their joint loss only when that loss is a mean over rays.  A coarse + fine
 pair is two passes with two sets of cotangents and is not taken.
@@ -40,7 +44,9 @@ class DifferentiableRender:
                              "detach them, or their gradient would silently lack the render's term")
         # the anchor makes the outputs require grad also when `parameters` does not: the backward has to run for the weights' sake
         anchor = torch.zeros((), device=torch.device("cuda", tr.device), requires_grad=True)
-        return _render_function().apply(anchor, parameters if wants else None, tr, (rays_o, rays_d, t, parameters, cone_scale), kw)
+        # inputs that take a gradient reach the function as direct arguments: autograd does not look inside the tuple
+        ins = [a if getattr(tr, "input_gradients", False) and isinstance(a, torch.Tensor) and a.requires_grad else None for a in (rays_o, rays_d)]
+        return _render_function().apply(anchor, parameters if wants else None, ins[0], ins[1], tr, (rays_o, rays_d, t, parameters, cone_scale), kw)
 
 
 class DifferentiableInstanceRender:
@@ -73,7 +79,9 @@ class DifferentiableInstanceRender:
             raise ValueError("params_map.requires_grad, but the trainer takes no parameter gradients (FlexTrainer / BranchTrainer with param_gradients=True or \"only\"); "
                              "detach it, or its gradient would silently lack the render's term")
         anchor = torch.zeros((), device=torch.device("cuda", tr.device), requires_grad=True)
-        return _render_function().apply(anchor, params_map if wants else None, tr, ("instanced", bufs[:9] + (params_map,), cone_scale), dict(self.opts, **kw))
+        ins = [a if getattr(tr, "input_gradients", False) and isinstance(a, torch.Tensor) and a.requires_grad else None for a in (bufs[1], bufs[0])]   # pts, rays_d_map
+        return _render_function().apply(anchor, params_map if wants else None, ins[0], ins[1], tr, ("instanced", bufs[:9] + (params_map,), cone_scale),
+                                        dict(self.opts, **kw))
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,18 +91,17 @@ def _render_function():
 
     class Render(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, anchor, held, trainer, args, kw):
+        def forward(ctx, anchor, held, in_a, in_b, trainer, args, kw):
             ctx.instanced = len(args) == 3 and isinstance(args[0], str)
             if ctx.instanced:                                        # ("instanced", the instancer's ten buffers, cone_scale)
                 _, bufs, cone_scale = args
                 bufs = tuple(b.detach() if isinstance(b, torch.Tensor) else b for b in bufs)
                 color, alpha = trainer.forward_instanced(bufs, cone_scale, **kw)
             else:
-                rays_o, rays_d, t, parameters, cone_scale = args
-                if isinstance(parameters, torch.Tensor):
-                    parameters = parameters.detach()
+                rays_o, rays_d, t, parameters, cone_scale = (a.detach() if isinstance(a, torch.Tensor) else a for a in args)
                 color, alpha = trainer.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
-            ctx.trainer, ctx.serial, ctx.like = trainer, trainer._pending[0], (None if held is None else (tuple(held.shape), held.device, held.dtype))
+            like = lambda x: None if x is None else (tuple(x.shape), x.device, x.dtype)
+            ctx.trainer, ctx.serial, ctx.like, ctx.like_in = trainer, trainer._pending[0], like(held), (like(in_a), like(in_b))
             return color, alpha
 
         @staticmethod
@@ -116,6 +123,10 @@ def _render_function():
                 grad = torch.zeros(shape, device=rows.device, dtype=rows.dtype)
                 grad.reshape(-1)[:rows.numel()].copy_(rows.reshape(-1))
                 grad = grad.to(device=device, dtype=dtype)
-            return None, grad, None, None, None
+            ins = [None, None]
+            if any(l is not None for l in ctx.like_in):              # (rays_o, rays_d) of a plain step, (pts, rays_d_map) of an instanced one
+                got = tr.sample_input_gradients() if ctx.instanced else tr.ray_gradients()
+                ins = [None if l is None else g.reshape(l[0]).to(device=l[1], dtype=l[2]) for g, l in zip(got, ctx.like_in)]
+            return None, grad, ins[0], ins[1], None, None, None
 
     return Render

@@ -4,7 +4,9 @@
 // parameter branch's output into the concatenations by flex_branch_copy_kernel; where it is asked for (ntx_trainer_enable_param_gradients), dL/d params:
 // one more term per reader of the parameter features, then flex_param_fold_kernel / flex_param_rows_kernel.  An instanced step
 // (ntx_train_forward_instanced) is the same network on the compact rows of the in-patch samples: flex_encode_samples_kernel in front,
-// flex_param_samples_kernel behind.  The handle, the composite, the loss and Adam are ntx_trainer.hip's.  gfx950 only.
+// flex_param_samples_kernel behind.  Where it is asked for (ntx_trainer_enable_input_gradients), dL/d rays_o, rays_d and -- of an instanced
+// step -- dL/d pts, rays_d_map: one more term per reader of FF(xyz) / FF(dir), then flex_ray_fold_kernel / flex_input_samples_kernel.
+// The handle, the composite, the loss and Adam are ntx_trainer.hip's.  gfx950 only.
 #include <algorithm>
 #include "ntx_trainer.h"
 #include "ntx_encode.h"
@@ -254,6 +256,88 @@ __global__ __launch_bounds__(256) void flex_param_samples_kernel(FlexSampleFoldA
     }
     args.out[e] = v;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// dL/d rays_o, rays_d and dL/d pts, rays_d_map (ntx_trainer_enable_input_gradients).  The way back leaves the gradient at the FF(xyz) rows
+// and the FF(dir) rows of every sample, IG_pos[M][ld_pos] / IG_dir[M][ld_dir]; a row goes through the encoder's derivative to a 3-vector --
+// component c: the identity row plus, per band, slope(sin row) and slope(cos row) at the value x_c the encoder fed (RayCtx::point /
+// RayCtx::dir) --, a_s for the position and b_s for the direction.  The sample depths are constants (renderer.py:129).
+// ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float fourier_back3(const float *row, int L, int c, float x) {
+    float v = row[c];
+    for (int f = 0; f < L; ++f) {
+        v = fmaf(fourier_slope(x, f, 0), row[fourier_row_of(3, f, 0, c)], v);
+        v = fmaf(fourier_slope(x, f, 1), row[fourier_row_of(3, f, 1, c)], v);
+    }
+    return v;
+}
+// The ray fold of a plain step, flex_param_fold_kernel's sibling: a wave per ray, lane l the samples l, l + 64, ... in ascending order, then
+// the lanes' butterfly; a wave's 64 samples are 64 consecutive rows of IG_pos and of IG_dir.  With n = d / |d| and B = sum_s b_s:
+//     d_rays_o = sum_s a_s,    d_rays_d = sum_s z_s a_s + (B - n (n . B)) / |d| + n dL/d|d|
+// dL/d|d| is the composite's dists = dz |d| (renderer.py:180): dL/d dist_s dist_s = dL/d sigma_s relu(sigma_s + noise_s), and dgrad[s][3]
+// is 0 where that ReLU is closed, so dL/d|d| = (sum_s dgrad[s][3] (sigma_s + noise_s)) / |d|.  A sample of a ray that misses (z not finite)
+// is SELECTED to 0, and so are both rows of a ray without a sample that hits: its cone_scale and its cotangent may be anything.  No sum
+// depends on the grid or on the trainer's capacity.
+struct FlexRayFoldArgs { StepRays r; const float *ig_pos, *ig_dir; int ld_pos, ld_dir; const float *dgrad, *sigma, *noise; float *d_rays_o, *d_rays_d; };
+__global__ __launch_bounds__(256) void flex_ray_fold_kernel(FlexRayFoldArgs args) {
+    const StepRays &a = args.r;
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= a.n_rays) return;
+    const RayCtx rc = ray_ctx(a.rays_d, a.params, a.rays_per_param_row, ray, a.n_geo + a.n_app);
+    const float *zray = a.z + (size_t)ray * a.S;
+    const float o[3] = {a.rays_o[3 * ray], a.rays_o[3 * ray + 1], a.rays_o[3 * ray + 2]};
+    const float *gp = args.ig_pos + (size_t)ray * a.S * args.ld_pos, *gd = args.ig_dir + (size_t)ray * a.S * args.ld_dir;
+    const size_t m0 = (size_t)ray * a.S;
+    float sa[3] = {0.0f, 0.0f, 0.0f}, sza[3] = {0.0f, 0.0f, 0.0f}, sb[3] = {0.0f, 0.0f, 0.0f}, q = 0.0f;
+    bool any = false;
+    for (int s = lane; s < a.S; s += 64) {
+        bool hit;
+        const float z = depth_of(zray[s], hit);
+        any = any || hit;
+        const float *prow = gp + (size_t)s * args.ld_pos, *drow = gd + (size_t)s * args.ld_dir;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float av = fourier_back3(prow, a.pos_freq, c, rc.point(o[c], c, z));
+            const float bv = fourier_back3(drow, a.dir_freq, c, rc.dir(c));
+            sa[c] += hit ? av : 0.0f; sza[c] += hit ? z * av : 0.0f; sb[c] += hit ? bv : 0.0f;
+        }
+        const float sg = args.noise ? args.sigma[m0 + s] + args.noise[m0 + s] : args.sigma[m0 + s];
+        const float dq = args.dgrad[4 * (m0 + s) + 3] * sg;
+        q += hit ? dq : 0.0f;
+    }
+    any = __any(any) != 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { sa[c] = wave_sumf(sa[c]); sza[c] = wave_sumf(sza[c]); sb[c] = wave_sumf(sb[c]); }
+    q = wave_sumf(q);
+    if (lane < 3) {
+        const float n[3] = {rc.dir(0), rc.dir(1), rc.dir(2)};
+        const float nb = (n[0] * sb[0] + n[1] * sb[1]) + n[2] * sb[2], dlen = q / rc.dn;
+        const float go = lane == 0 ? sa[0] : lane == 1 ? sa[1] : sa[2];
+        const float gz = lane == 0 ? sza[0] : lane == 1 ? sza[1] : sza[2], gb = lane == 0 ? sb[0] : lane == 1 ? sb[1] : sb[2];
+        const float nc = lane == 0 ? n[0] : lane == 1 ? n[1] : n[2];
+        const float gd3 = (gz + (gb - nc * nb) / rc.dn) + nc * dlen;
+        args.d_rays_o[3 * ray + lane] = any ? go : 0.0f;
+        args.d_rays_d[3 * ray + lane] = any ? gd3 : 0.0f;
+    }
+}
+// The same of an instanced step, flex_param_samples_kernel's sibling: nothing is added up -- d_pts[m] = a and d_dirs[m] = b of live sample m's
+// compact row (the direction is fed as given: no normalisation term; dists are the caller's: no |d| term); a sample that is not live is
+// written as 0 and nothing of it is read.  Thread per (sample, component): 0..2 the position's, 3..5 the direction's.
+struct FlexSampleInputArgs { StepSamples s; const float *ig_pos, *ig_dir; int ld_pos, ld_dir; float *d_pts, *d_dirs; };
+__global__ __launch_bounds__(256) void flex_input_samples_kernel(FlexSampleInputArgs args) {
+    const StepSamples &a = args.s;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.M() * 6) return;
+    const long long m = e / 6;
+    const int k = (int)(e - m * 6), c = k < 3 ? k : k - 3, row_i = a.row_of[m];
+    float v = 0.0f;
+    if (row_i >= 0) {
+        if (k < 3) v = fourier_back3(args.ig_pos + (size_t)row_i * args.ld_pos, a.pos_freq, c, a.pts[3 * m + c]);
+        else v = fourier_back3(args.ig_dir + (size_t)row_i * args.ld_dir, a.dir_freq, c, a.rays_d_map[3 * m + c]);
+    }
+    (k < 3 ? args.d_pts : args.d_dirs)[3 * m + c] = v;
+}
 }   // namespace ntx_train
 namespace {
 using namespace ntx_train;
@@ -269,6 +353,7 @@ struct FlexLayer {
     long long wt = -1;                                  // its transposed hidden rows [out][in - enc] in FlexBackend::wt
     long long bwt = -1;                                 // a consumer of a parameter branch: its transposed branch rows [out][param_width] in FlexBackend::wt
     long long pwt = -1;                                 // parameter gradients on: a reader of parameter features, its transposed feature rows [out][n_in]; a branch's layer 0, its kernel whole
+    long long xwt = -1;                                 // input gradients on: a reader of pos_map / dir_map, its transposed FF(xyz) / FF(dir) rows [out][K3]
 };
 // A parameter branch (model.py:88-93 geometry, 96-101 appearance): param_depth Dense(param_width, relu) layers on FF(parameters), per sample
 // (with blur_idx on one of its parameters the input differs from sample to sample).  Layer j's X is the input buffer / layer j - 1's Y; every Y
@@ -296,6 +381,7 @@ struct FlexBackend : Backend {
     std::vector<FlexTSeg> segs;                         // the table on the host: enable_param_gradients appends to it
     float *PG[2] = {nullptr, nullptr}; int ldpg[2] = {0, 0}, pg_met[2] = {0, 0};      // the gradient at the geometry / appearance parameter features [M][pad4(n_in)]; readers met on this way back
     float *ray_pg = nullptr;                            // [cap_rays][P]: a ray's samples folded and added
+    float *IG[2] = {nullptr, nullptr}; int ldig[2] = {0, 0}, ig_met[2] = {0, 0}, K3[2] = {0, 0};       // the gradient at the FF(xyz) / FF(dir) rows [M][pad4(K3)]; readers met on this way back
     float *partial = nullptr, *colsum = nullptr;        // [n_split][in * out], [n_split][out] of the layer whose weight gradient is being taken
     FlexDst pos_dst[FLEX_MAX_DST]; int n_pos_dst = 0; FlexDst dir_dst{};
     size_t plan(const ntx_model_desc *d, int param_depth, int param_width);
@@ -306,6 +392,8 @@ struct FlexBackend : Backend {
     void param_term(int group, long long pwt, int n_in, const float *dY, int lddy, int K, long long M, hipStream_t st);
     void seg(long long &slot, size_t src, int rows, int out);
     int enable_param_gradients() override;
+    int enable_input_gradients() override;
+    void input_term(int group, const FlexLayer &l, const float *dY, long long M, hipStream_t st);
     void reduce(hipStream_t st, int n_split, const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out);
     void network_forward(long long M, hipStream_t st);                      // the rows are encoded: branches, layers, heads on M rows
     void network_backward(long long M, hipStream_t st);                     // dgrad [M][4] -> the weight gradients, the gradient at the parameter features
@@ -449,6 +537,33 @@ int FlexBackend::enable_param_gradients() {
     return mem.rc;
 }
 
+// What dL/d rays and sample points needs, placed at the first enable for the trainer's capacity: the gradients at the FF(xyz) and FF(dir)
+// rows, a plain step's two results, and the transposed first K3 rows of every reader's kernel (trunk layer 0 and the layers behind a skip read
+// FF(xyz), the first layer that reads dir_map FF(dir); with or without branches) as NEW segments behind the table's last, as above
+int FlexBackend::enable_input_gradients() {
+    if (IG[0]) return NTX_OK;
+    DeviceMemory &mem = t->mem;
+    const ntx_model_desc &d = t->desc;
+    TRAIN_TRY(hipSetDevice(t->device));
+    K3[0] = 3 * (1 + 2 * d.pos_freq); K3[1] = 3 * (1 + 2 * d.dir_freq);
+    for (int k = 0; k < 2; ++k) {
+        ldig[k] = pad4(K3[k]);
+        mem.alloc(&IG[k], (size_t)t->cap * ldig[k]);
+        for (size_t i = 0; i < layers.size(); ++i) {
+            FlexLayer &l = layers[i];
+            const bool reads = k == 0 ? (int)i < d.depth && l.enc > 0 : (int)i == d.depth + 1;
+            if (reads) seg(l.xwt, l.w, K3[k], l.out);
+        }
+    }
+    mem.alloc(&t->d_rays_o, (size_t)t->cap_rays * 3); mem.alloc(&t->d_rays_d, (size_t)t->cap_rays * 3);
+    float *old_wt = wt; FlexTSeg *old_seg = tseg;
+    n_tseg = (int)segs.size();
+    mem.alloc(&wt, (size_t)t_total);                                         // (every forward pass fills it again)
+    mem.upload(&tseg, segs, "segment");
+    if (mem.rc == NTX_OK) { mem.release(old_wt); mem.release(old_seg); }
+    return mem.rc;
+}
+
 // a branch's layers, then its last output into the concatenations that hold the map
 void FlexBackend::branch_forward(const FlexBranch &b, const FlexDst *dst, int n_dst, long long M, hipStream_t st) {
     const float *W = t->w;
@@ -530,6 +645,12 @@ void FlexBackend::param_term(int group, long long pwt, int n_in, const float *dY
     g.accumulate = pg_met[group]++ > 0;
     launch_gemm(st, true, g);
 }
+// A reader's term of the gradient at the FF(xyz) rows (group 0) or the FF(dir) rows (1): IG (+)= dY . W[first K3 rows]^T, in the same order
+void FlexBackend::input_term(int group, const FlexLayer &l, const float *dY, long long M, hipStream_t st) {
+    GemmArgs g{}; g.A = dY; g.lda = ldg; g.B = wt + l.xwt; g.ldb = K3[group]; g.C = IG[group]; g.ldc = ldig[group]; g.M = (int)M; g.N = K3[group]; g.K = l.out;
+    g.accumulate = ig_met[group]++ > 0;
+    launch_gemm(st, true, g);
+}
 // ... and from there through the branch, as through the trunk: dW / db per layer over ranges of FLEX_SPLIT samples, dX masked by the layer in
 // front; nothing behind the first layer (the inputs are not trained)
 void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split, hipStream_t st) {
@@ -537,7 +658,7 @@ void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split,
     for (int j = (int)b.layers.size() - 1; j >= 0; --j) {
         const FlexLayer &l = b.layers[j];
         const float *dY = BG[cur];
-        if (t->pg_mode != 2) {
+        if (t->takes_weight_gradients()) {
             GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldb; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
             g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
             launch_gemm(st, false, g, n_split);
@@ -564,16 +685,25 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
         hipLaunchKernelGGL(flex_param_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
         hipLaunchKernelGGL(flex_param_rows_kernel, dim3((unsigned)((rows * P + 255) / 256)), dim3(256), 0, st, ray_pg, r.n_rays, r.rays_per_param_row, P, rows, t->param_grad);
     }
+    if (t->ig_mode != 0) {                                                   // the FF(xyz) / FF(dir) rows' gradient through the encoder, a ray's samples
+        FlexRayFoldArgs f{}; f.r = r; f.ig_pos = IG[0]; f.ig_dir = IG[1]; f.ld_pos = ldig[0]; f.ld_dir = ldig[1]; f.dgrad = t->dgrad; f.sigma = t->sigma;
+        f.noise = t->step_noise; f.d_rays_o = t->d_rays_o; f.d_rays_d = t->d_rays_d;
+        hipLaunchKernelGGL(flex_ray_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
+    }
     return NTX_OK;
 }
 // An instanced step's way back over its n_live rows.  Without a live sample nothing is contracted: every weight gradient is exactly 0 (mode
 // 2 leaves the buffer alone, as ever), and the per-sample parameter gradients are zeros.
 int FlexBackend::backward_samples(const StepSamples &s, float *sample_pg, hipStream_t st) {
     if (s.n_live > 0) network_backward(s.n_live, st);
-    else if (t->pg_mode != 2) TRAIN_TRY(hipMemsetAsync(t->grad, 0, t->n_weights * sizeof(float), st));
+    else if (t->takes_weight_gradients()) TRAIN_TRY(hipMemsetAsync(t->grad, 0, t->n_weights * sizeof(float), st));
     if (t->pg_mode != 0) {
         FlexSampleFoldArgs f{}; f.s = s; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.out = sample_pg;
         hipLaunchKernelGGL(flex_param_samples_kernel, dim3((unsigned)((s.M() * t->P + 255) / 256)), dim3(256), 0, st, f);
+    }
+    if (t->ig_mode != 0) {                                                   // (no live sample: every row_of is -1, both results are zeros)
+        FlexSampleInputArgs f{}; f.s = s; f.ig_pos = IG[0]; f.ig_dir = IG[1]; f.ld_pos = ldig[0]; f.ld_dir = ldig[1]; f.d_pts = t->d_pts; f.d_dirs = t->d_dirs;
+        hipLaunchKernelGGL(flex_input_samples_kernel, dim3((unsigned)((s.M() * 6 + 255) / 256)), dim3(256), 0, st, f);
     }
     return NTX_OK;
 }
@@ -583,8 +713,8 @@ void FlexBackend::network_backward(long long M, hipStream_t st) {
     auto reduce = [&](const float *part, long long count, size_t out, const float *bias_partial, long long bias_count, size_t bias_out) {
         this->reduce(st, n_split, part, count, out, bias_partial, bias_count, bias_out);
     };
-    geo.consumers_met = app.consumers_met = 0; pg_met[0] = pg_met[1] = 0;
-    const bool wgrad = t->pg_mode != 2, pgrad = t->pg_mode != 0;               // mode 2: dL/d params alone, no weight gradient is taken or reduced
+    geo.consumers_met = app.consumers_met = 0; pg_met[0] = pg_met[1] = 0; ig_met[0] = ig_met[1] = 0;
+    const bool wgrad = t->takes_weight_gradients(), pgrad = t->pg_mode != 0;   // either mode 2: no weight gradient is taken or reduced
     const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
     const unsigned ew = 256;
     // the colour head (model.py:123): kernel and bias lie side by side in the blob, as in a range's partial sums
@@ -613,7 +743,8 @@ void FlexBackend::network_backward(long long M, hipStream_t st) {
             const int group = i <= last_trunk ? 0 : 1;
             param_term(group, l.pwt, (group == 0 ? geo : app).n_in, dY, ldg, l.out, M, st);
         }
-        if (i == 0) break;                                                   // positions and directions take no gradient
+        if (t->ig_mode != 0 && l.xwt >= 0) input_term(i <= last_trunk ? 0 : 1, l, dY, M, st);      // a reader of FF(xyz) / FF(dir): its term, in the same order
+        if (i == 0) break;
         const FlexLayer &s = layers[l.src];
         float *dX = G[cur ^ 1];
         int accumulate = 0;

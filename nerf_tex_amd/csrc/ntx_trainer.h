@@ -80,6 +80,12 @@ struct Backend {
         return ntx_set_error(NTX_E_UNSUPPORTED, "parameter gradients: the fused chain (ntx_trainer_create) stops at the encoded inputs; the layer-by-layer "
                              "trainer takes the same model (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
     }
+    // ntx_trainer_enable_input_gradients, mode 1 / 2: places what dL/d rays_o, rays_d (a plain step) and dL/d pts, rays_d_map (an instanced
+    // one) need (once); the handle keeps the mode
+    virtual int enable_input_gradients() {
+        return ntx_set_error(NTX_E_UNSUPPORTED, "input gradients: the fused chain (ntx_trainer_create) stops at the encoded inputs; the layer-by-layer "
+                             "trainer takes the same model (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
+    }
 };
 // what an entry's architecture check makes of a descriptor
 struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; int param_depth, param_width; };   // param_*: the branches the model HAS (0 without parameters)
@@ -106,6 +112,14 @@ struct ntx_trainer {
     // workspace, and -- at the first instanced backward under pg_mode 1 / 2 -- the per-sample dL/d params [N][S][P] (spg_rays = 0: no such step yet)
     int *live = nullptr, *row_of = nullptr, *ray_live = nullptr; long long *n_live_dev = nullptr;
     float *sample_pg = nullptr; long long spg_rays = 0; int spg_S = 0;
+    // ntx_trainer_enable_input_gradients: 0 off, 1 dL/d rays and sample points beside the weight gradients, 2 without them.  d_rays_o / d_rays_d
+    // [cap_rays][3] of the last plain step (the backend places them at the first enable; ig_rays = 0: no such step yet), d_pts / d_dirs [cap][3]
+    // of the last instanced one (placed at the first instanced backward under the mode; ig_smp_rays = 0: no such step yet)
+    int ig_mode = 0;
+    float *d_rays_o = nullptr, *d_rays_d = nullptr, *d_pts = nullptr, *d_dirs = nullptr;
+    long long ig_rays = 0, ig_smp_rays = 0; int ig_S = 0;
+    const float *step_noise = nullptr;         // the density noise of the step whose way back runs (NULL without NTX_FLAG_RAW_NOISE): the ray fold's |d| term reads it
+    bool takes_weight_gradients() const { return pg_mode != 2 && ig_mode != 2; }   // the weight gradient is taken unless EITHER mode is 2
     long long adam_iterations = 0;
     // ntx_train_forward's step until its ntx_train_backward: the caller's rays (alive and unchanged until then), what the composite was run with;
     // samples: the step is ntx_train_forward_instanced's, and smp holds the caller's buffers instead of rays

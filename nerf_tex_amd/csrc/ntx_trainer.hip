@@ -524,8 +524,12 @@ __global__ void add_kernel(float *__restrict__ dst, const float *__restrict__ sr
 }
 }   // namespace ntx_train
 
-// mode 2 of ntx_trainer_enable_param_gradients takes no weight gradient: what would use one says so
+// mode 2 of ntx_trainer_enable_param_gradients takes no weight gradient: what would use one says so (as does mode 2 of
+// ntx_trainer_enable_input_gradients)
 static int no_weight_gradients(const ntx_trainer *t, const char *who) {
+    if (t->ig_mode == 2)
+        return ntx_set_error(NTX_E_INVALID, "%s: the trainer takes input gradients only (ntx_trainer_enable_input_gradients mode 2), its weight gradient is not this "
+                             "step's; set mode 0 or 1 first", who);
     return t->pg_mode == 2 ? ntx_set_error(NTX_E_INVALID, "%s: the trainer takes parameter gradients only (ntx_trainer_enable_param_gradients mode 2), its weight gradient is "
                                            "not this step's; set mode 0 or 1 first", who) : NTX_OK;
 }
@@ -586,6 +590,7 @@ static int step_network(ntx_trainer *t, const float *rays_o, const float *rays_d
         if (rc != NTX_OK) return rc;
         *noise = t->noise;
     }
+    t->step_noise = *noise;
     const ntx_model_desc &d = t->desc;
     *rays = StepRays{rays_o, rays_d, z, params, cone_scale, rays_per_param_row, n_rays, S, blur_idx, d.n_geo, d.n_app, d.pos_freq, d.dir_freq, d.param_freq};
     return t->backend->forward(*rays, (hipStream_t)stream);
@@ -612,12 +617,17 @@ static InstCompositeArgs inst_composite_args(const ntx_trainer *t, const StepSam
 static int backward_instanced(ntx_trainer *t, const float *d_color, const float *d_alpha, hipStream_t st) {
     const StepSamples &s = t->pending.smp;
     if (t->pg_mode != 0 && !t->sample_pg && t->mem.alloc(&t->sample_pg, (size_t)t->cap * t->P) != NTX_OK) return t->mem.rc;
+    if (t->ig_mode != 0 && !t->d_pts) {
+        t->mem.alloc(&t->d_pts, (size_t)t->cap * 3); t->mem.alloc(&t->d_dirs, (size_t)t->cap * 3);
+        if (t->mem.rc != NTX_OK) return t->mem.rc;
+    }
     const InstCompositeArgs c = inst_composite_args(t, s, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
     if (s.n_live > 0) hipLaunchKernelGGL(inst_composite_adjoint_kernel, dim3((unsigned)((s.n_rays + 3) / 4)), dim3(256), 0, st, c, d_color, d_alpha);
     int rc = t->backend->backward_samples(s, t->sample_pg, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
     if (t->pg_mode != 0) { t->spg_rays = s.n_rays; t->spg_S = s.S; t->pg_rows = 0; }
+    if (t->ig_mode != 0) { t->ig_smp_rays = s.n_rays; t->ig_S = s.S; t->ig_rays = 0; }
     return NTX_OK;
 }
 
@@ -648,6 +658,7 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
     if (t->pg_mode != 0) { t->pg_rows = (n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row; t->spg_rays = 0; }
+    if (t->ig_mode != 0) { t->ig_rays = n_rays; t->ig_smp_rays = 0; }
     return NTX_OK;
 }
 
@@ -680,11 +691,13 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
     const StepRays &rays = t->pending.rays;
     CompositeArgs c = composite_args(t, rays, t->pending.noise, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
     c.weights = nullptr;                                                                        // (b) alone: nothing of the forward is written again
+    t->step_noise = t->pending.noise;
     hipLaunchKernelGGL(composite_adjoint_kernel, dim3((unsigned)((rays.n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c, d_color, d_alpha);
     int rc = t->backend->backward(rays, (hipStream_t)stream);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
     if (t->pg_mode != 0) { t->pg_rows = (rays.n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row; t->spg_rays = 0; }
+    if (t->ig_mode != 0) { t->ig_rays = rays.n_rays; t->ig_smp_rays = 0; }
     return NTX_OK;
 }
 
@@ -756,6 +769,34 @@ int ntx_trainer_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t 
                                                                  (t->spg_rays ? "the last step was an instanced one (ntx_trainer_sample_param_gradients has its per-sample gradients)" :
                                                                   "no step has run since they were enabled"));
     *grad_dev = t->param_grad; *rows = t->pg_rows; *n_params = t->P;
+    return NTX_OK;
+}
+
+int ntx_trainer_enable_input_gradients(ntx_trainer *t, int mode) {
+    if (!t || mode < 0 || mode > 2) return ntx_set_error(NTX_E_INVALID, "trainer is NULL or mode is not 0 (off) / 1 (with the weight gradients) / 2 (inputs only)");
+    if (mode != 0) {
+        int rc = t->backend->enable_input_gradients();                                          // the chain refuses; the layer-by-layer backend places its buffers once
+        if (rc != NTX_OK) return rc;
+    } else { t->ig_rays = 0; t->ig_smp_rays = 0; }
+    if (mode != t->ig_mode) t->pending.open = false;                                           // (the first enable re-places the transposed weights a pending forward filled)
+    t->ig_mode = mode;
+    return NTX_OK;
+}
+
+int ntx_trainer_ray_gradients(ntx_trainer *t, const float **d_rays_o, const float **d_rays_d, int64_t *n_rays) {
+    if (!t || !d_rays_o || !d_rays_d || !n_rays) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (t->ig_mode == 0 || t->ig_rays == 0) return ntx_set_error(NTX_E_INVALID, "no ray gradients: %s", t->ig_mode == 0 ? "ntx_trainer_enable_input_gradients is off" :
+                                                                 (t->ig_smp_rays ? "the last step was an instanced one (ntx_trainer_sample_input_gradients has its per-sample gradients)" :
+                                                                  "no step has run since they were enabled"));
+    *d_rays_o = t->d_rays_o; *d_rays_d = t->d_rays_d; *n_rays = t->ig_rays;
+    return NTX_OK;
+}
+
+int ntx_trainer_sample_input_gradients(ntx_trainer *t, const float **d_pts, const float **d_dirs, int64_t *n_rays, int *n_samples) {
+    if (!t || !d_pts || !d_dirs || !n_rays || !n_samples) return ntx_set_error(NTX_E_INVALID, "NULL argument");
+    if (t->ig_mode == 0 || t->ig_smp_rays == 0) return ntx_set_error(NTX_E_INVALID, "no per-sample input gradients: %s", t->ig_mode == 0 ? "ntx_trainer_enable_input_gradients is off" :
+                                                                     "the last step since they were enabled was not an instanced one (ntx_trainer_ray_gradients has a plain step's)");
+    *d_pts = t->d_pts; *d_dirs = t->d_dirs; *n_rays = t->ig_smp_rays; *n_samples = t->ig_S;
     return NTX_OK;
 }
 

@@ -388,15 +388,20 @@ class FlexTrainer(Trainer):
     _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create_flex(*a))
     _widen = staticmethod(lambda model: None)                                      # every width trains as it is
 
-    def __init__(self, model, *args, param_gradients=False, **kw) -> None:
+    def __init__(self, model, *args, param_gradients=False, input_gradients=False, **kw) -> None:
         """`Trainer`'s arguments, and `param_gradients`: False, True -- every `gradients_step` also leaves dL/d parameters
         (`parameter_gradients()`), the weight gradients bit for bit as without it -- or "only": the same parameter gradients and no weight
         gradient at all (`gradients()` keeps what it held; `apply_gradients` raises NTX_E_INVALID).  For a model with parameters
-        (`ntx_trainer_enable_param_gradients`)."""
+        (`ntx_trainer_enable_param_gradients`).  `input_gradients`: the same three values for dL/d rays_o, rays_d (`ray_gradients()`) and,
+        of an instanced step, dL/d pts, rays_d_map (`sample_input_gradients()`), for any model (`ntx_trainer_enable_input_gradients`); no
+        weight gradient is taken while either is "only"."""
         super().__init__(model, *args, **kw)
         self.param_gradients = False
+        self.input_gradients = False
         if param_gradients is not False:
             self.set_param_gradients(param_gradients)
+        if input_gradients is not False:
+            self.set_input_gradients(input_gradients)
 
     def set_param_gradients(self, mode) -> None:
         """False / True / "only" for the following steps (the buffers are placed at the first True or "only")."""
@@ -409,6 +414,43 @@ class FlexTrainer(Trainer):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib.ntx_trainer_enable_param_gradients(self._h, native))
         self.param_gradients = "only" if native == 2 else bool(native)
+
+    def set_input_gradients(self, mode) -> None:
+        """False / True / "only" for the following steps (the buffers are placed at the first True or "only")."""
+        modes = {False: 0, True: 1, "only": 2}
+        if isinstance(mode, (int, str)) and mode in modes:
+            native = modes[mode]
+        else:
+            raise ValueError(f'input_gradients must be False, True or "only", not {mode!r}')
+        import torch
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.ntx_trainer_enable_input_gradients(self._h, native))
+        self.input_gradients = "only" if native == 2 else bool(native)
+
+    def _device_copies(self, ptrs, shape):
+        """Copies of the trainer's device results `ptrs` as torch tensors of `shape`, in the current stream's order."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        outs = tuple(torch.empty(shape, device=dev, dtype=torch.float32) for _ in ptrs)
+        with torch.cuda.device(dev):
+            for out, ptr in zip(outs, ptrs):
+                if out.numel():
+                    _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
+        return outs
+
+    def ray_gradients(self):
+        """(dL/d rays_o, dL/d rays_d) of the last plain step: torch tensors [N, 3] on the trainer's device, copies in the current stream's
+        order.  The sample depths are constants; a ray that misses has exact zeros."""
+        o, d, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        _lib.check(_lib.lib.ntx_trainer_ray_gradients(self._h, C.byref(o), C.byref(d), C.byref(n)))
+        return self._device_copies((o, d), (int(n.value), 3))
+
+    def sample_input_gradients(self):
+        """(dL/d pts, dL/d rays_d_map) of the last INSTANCED step: torch tensors [N, S, 3] on the trainer's device (exact zeros at samples
+        outside every patch), copies in the current stream's order."""
+        p, d, n, s = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int()
+        _lib.check(_lib.lib.ntx_trainer_sample_input_gradients(self._h, C.byref(p), C.byref(d), C.byref(n), C.byref(s)))
+        return self._device_copies((p, d), (int(n.value), int(s.value), 3))
 
     def parameter_gradients(self):
         """dL/d parameters of the last step: a torch tensor [rows, P] on the trainer's device (rows = the step's parameter rows,
@@ -539,14 +581,14 @@ def _chain_takes(model) -> bool:
     return _widened(model) is not None and model.n_pos == 3
 
 
-def trainer_class_for(model, branches: bool = False, param_gradients=False):
+def trainer_class_for(model, branches: bool = False, param_gradients=False, input_gradients=False):
     """The class that trains `model`, without creating anything (no device is asked for): `Trainer` where the fused chain takes it,
     `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise -- which is what a
     model with parameter branches gets unless `branches` is set: then a model with param_depth > 0 and at least one parameter gets
-    `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it.  `param_gradients` (True or "only"): the layer-by-layer class also where
-    the chain would take the model -- the chain stops at the encoded inputs."""
+    `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it.  `param_gradients` / `input_gradients` (True or "only"): the layer-by-layer class also
+    where the chain would take the model -- the chain stops at the encoded inputs."""
     import numpy as np
-    if _chain_takes(model) and param_gradients is False:
+    if _chain_takes(model) and param_gradients is False and input_gradients is False:
         return Trainer
     cls = BranchTrainer if branches and model.param_depth > 0 and model.n_params > 0 else FlexTrainer
     desc, h = model.desc(), C.c_void_p()
@@ -560,10 +602,11 @@ def trainer_class_for(model, branches: bool = False, param_gradients=False):
 
 def trainer_for(model, **kw):
     """`Trainer(model, **kw)`, `FlexTrainer(model, **kw)` or `BranchTrainer(model, **kw)`, whichever `trainer_class_for(model, branches=True)`
-    names; with `param_gradients=True` / "only" the layer-by-layer class in any case (it is the one that takes them)."""
-    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False))
+    names; with `param_gradients` or `input_gradients` True / "only" the layer-by-layer class in any case (it is the one that takes them)."""
+    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False), input_gradients=kw.get("input_gradients", False))
     if cls is Trainer:
         kw.pop("param_gradients", None)                                        # (False: the chain has no such argument)
+        kw.pop("input_gradients", None)
     return cls(model, **kw)
 
 
@@ -573,7 +616,8 @@ class CoarseFineTrainer:
     n_samples + n_importance merged depths by `model_fine` -- or by the same network when there is none (:132) -- and the loss of both
     passes added up.  Two networks take one step each, on their own gradients; one network takes one step on the sum of the two passes'.
     Every piece is the C ABI's: two `ntx_train_step_gradients` (the coarse one also leaves the weights: `ntx_trainer_composite_weights`),
-    `ntx_sample_pdf` between them, `ntx_trainer_stash_gradients` for the shared network."""
+    `ntx_sample_pdf` between them, `ntx_trainer_stash_gradients` for the shared network.  Input gradients (`input_gradients=`) are out of
+    scope here: two steps give two results to add, and each pass's trainer holds only its own."""
 
     def __init__(self, model, model_fine=None, max_rays: int = 1024, n_samples: int = 64, n_importance: int = 64, **kw) -> None:
         self.n_samples, self.n_importance, self.shared = int(n_samples), int(n_importance), model_fine is None

@@ -8,9 +8,12 @@ AlphaLoss(smape, mse) + Adam, timed with HIP events over whole steps:
     P0 P1 P2  the carpet model through FlexTrainer with parameter gradients off / beside the weight gradients / alone (`param_gradients=False, True,
               "only"`): P0 is B's step again; P2 has no weight gradient, so no Adam step -- it is `gradients_step` alone, and P0g is P0's
               `gradients_step` alone beside it (P2 / P0g: what the weight gradients are of a step)
-A and B alternate twice in one process so that clock drift shows, and so do the P runs.
+    I0 I1 I2  the same with input gradients (dL/d rays_o, rays_d: `input_gradients=False, True, "only"`): I0 is B's step again, I0g its
+              `gradients_step` alone, I2 has no weight gradient and no Adam step.  Nothing of the new path has been tuned.
+A and B alternate twice in one process so that clock drift shows, and so do the P and the I runs.
     python tools/bench_train_flex.py [--steps 20] [--warmup 5] [--only B] [--out profiles/train_flex/bench.json]
     python tools/bench_train_flex.py --only P --out profiles/train_flex/bench_param_gradients.json
+    python tools/bench_train_flex.py --only I --out profiles/input_gradients/bench.json
 One JSON line: per run ms a step, ray-samples/s and the fraction of the f32 matrix cores' peak the FLOPs a step needs take (bench.py's
 convention for training: 2 x forward + forward less the encoded inputs' rows)."""
 
@@ -50,6 +53,18 @@ def param_flops(model, samples, only):
     return step_flops(model, samples) + 2.0 * samples * (terms - (model.macs_per_sample() if only else 0))
 
 
+def input_flops(model, samples, only):
+    """`step_flops` with the readers' terms of dL/d rays (dY . W[first K3 rows]^T: 3 (1 + 2 pos_freq) = 63 columns at trunk layer 0 and the layers
+    behind a skip, 3 (1 + 2 dir_freq) = 27 at the layer behind the feature layer); `only`: forward + dX alone, no weight gradient."""
+    table = model.layer_table()
+    names = [name for name, _, _ in table]
+    behind_feature = names[names.index("feature") + 1]
+    k3p, k3d = 3 * (1 + 2 * model.pos_freq), 3 * (1 + 2 * model.dir_freq)
+    terms = sum((k3p if name.startswith("trunk") else k3d) * o for name, i, o in table
+                if (name.startswith("trunk") and (name == "trunk0" or i > model.width)) or name == behind_feature)
+    return step_flops(model, samples) + 2.0 * samples * (terms - (model.macs_per_sample() if only else 0))
+
+
 def time_steps(tr, args, loss, steps, warmup, gradients_only=False, **kw):
     one = tr.gradients_step if gradients_only else tr.step
     for _ in range(warmup):
@@ -68,7 +83,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--only", default=None, help="one of A B C D E (a profiler's run), or P: the parameter-gradient runs")
+    ap.add_argument("--only", default=None, help="one of A B C D E (a profiler's run), P: the parameter-gradient runs, or I: the input-gradient runs")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
     from nerf_tex_amd import synthetic
@@ -93,17 +108,20 @@ def main():
             "E": (BranchTrainer, seeded(ParamNerf(emb(10), emb(4), emb(4), [1, 6], param_depth=2)["model"]))}
     modes = {"P0": False, "P0g": False, "P1": True, "P2": "only"}
     runs.update({k: (FlexTrainer, carpet) for k in modes})
-    p_order = ["P0", "P0g", "P1", "P2"] * 2
-    order = p_order if a.only == "P" else [a.only] if a.only else ["A", "B", "A", "B", "C", "D", "E", "B", "E"] + p_order
+    imodes = {"I0": False, "I0g": False, "I1": True, "I2": "only"}
+    runs.update({k: (FlexTrainer, carpet) for k in imodes})
+    p_order, i_order = ["P0", "P0g", "P1", "P2"] * 2, ["I0", "I0g", "I1", "I2"] * 2
+    order = p_order if a.only == "P" else i_order if a.only == "I" else [a.only] if a.only else ["A", "B", "A", "B", "C", "D", "E", "B", "E"] + p_order
     out = {"what": "training step, 1024 rays x 256 samples, perturb, AlphaLoss(smape, mse) + Adam; HIP events", "steps": a.steps, "warmup": a.warmup, "runs": []}
     trainers = {}
     for key in order:
         cls, model = runs[key]
         if key not in trainers:
-            trainers[key] = cls(model, max_rays=n, n_samples=S, lrate=5e-4, lrate_decay=500, perturb=True, **({"param_gradients": modes[key]} if modes.get(key) else {}))
+            trainers[key] = cls(model, max_rays=n, n_samples=S, lrate=5e-4, lrate_decay=500, perturb=True, **({"param_gradients": modes[key]} if modes.get(key) else {}),
+                                **({"input_gradients": imodes[key]} if imodes.get(key) else {}))
         batch = (d(ro), d(rd), d(t), d(params) if model.n_params else None, d(cone), d(color), d(alpha))
-        sec = time_steps(trainers[key], batch, loss, a.steps, a.warmup, gradients_only=key in ("P0g", "P2"), rays_per_param_row=R)
-        fl = param_flops(model, n * S, key == "P2") if modes.get(key) else step_flops(model, n * S)
+        sec = time_steps(trainers[key], batch, loss, a.steps, a.warmup, gradients_only=key in ("P0g", "P2", "I0g", "I2"), rays_per_param_row=R)
+        fl = param_flops(model, n * S, key == "P2") if modes.get(key) else input_flops(model, n * S, key == "I2") if imodes.get(key) else step_flops(model, n * S)
         out["runs"].append({"run": key, "trainer": cls.__name__,
                             "model": f"{'Nerf' if model.kind else 'ParamNerf'} {model.depth} x {model.width}" + (f" param_depth {model.param_depth}" if model.param_depth else ""), "ms_step": 1e3 * sec,
                             "ray_samples_per_s": n * S / sec, "gflop_step": fl / 1e9, "fraction_of_f32_mfma_peak": fl / sec / PEAK_F32_MFMA})
@@ -116,6 +134,10 @@ def main():
         out["P1_over_P0"] = float(np.mean(ms("P1")) / np.mean(ms("P0")))
         out["P2_over_P0g"] = float(np.mean(ms("P2")) / np.mean(ms("P0g")))
         out["weight_gradient_share_of_flops"] = float(1.0 - param_flops(carpet, n * S, True) / param_flops(carpet, n * S, False))
+    if ms("I0") and ms("I1") and ms("I2"):
+        out["I1_over_I0"] = float(np.mean(ms("I1")) / np.mean(ms("I0")))
+        out["I2_over_I0g"] = float(np.mean(ms("I2")) / np.mean(ms("I0g")))
+        out["input_gradient_gflop_step"] = float((input_flops(carpet, n * S, False) - step_flops(carpet, n * S)) / 1e9)
     line = json.dumps(out)
     print(line)
     if a.out:
