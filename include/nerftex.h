@@ -738,6 +738,24 @@ int ntx_trainer_ray_gradients(ntx_trainer *t, const float **d_rays_o, const floa
 /* Where the last INSTANCED step left them: d_pts[n_rays][n_samples][3] and d_dirs[n_rays][n_samples][3] (dL/d rays_d_map), as above.
  * NTX_E_INVALID in mode 0, or when the last step since the enable was not an instanced one. */
 int ntx_trainer_sample_input_gradients(ntx_trainer *t, const float **d_pts, const float **d_dirs, int64_t *n_rays, int *n_samples);
+/* Both gradient modes at once, for either kind of handle (ABI v7, appended): param_mode and input_mode are the modes of
+ * ntx_trainer_enable_param_gradients and ntx_trainer_enable_input_gradients -- each 0 off, 1 beside the weight gradients, 2 without them --
+ * with the semantics stated there, and ntx_trainer_param_gradients / ntx_trainer_ray_gradients hand out the results as they are.  On a handle
+ * of ntx_trainer_create_flex / _flex_ex it does what those two entries do, one after the other.  On a handle of ntx_trainer_create it is the
+ * way in: the fused 8 x 256 chain keeps the gradient at every layer's output, and one more matrix-core kernel behind the chain back takes the
+ * three products it leaves out -- dy0 . W_trunk0[pos_map rows]^T + dy5 . W_trunk5[pos_map rows]^T and d c1o . W_C1[dir_map rows]^T per sample,
+ * each sum in a fixed order of its own (bit-reproducible, independent of the grid and of the trainer's capacity) -- into row-major buffers
+ * that the layer-by-layer backend's own folds then read (ntx_trainer_activation slots 40 / 41 after such a step: [n][Kp], [n][Kd]).  With
+ * both modes 0 a chain handle allocates and launches exactly what it does without this entry; the buffers are placed at the first non-zero
+ * mode, for the trainer's capacity.  Mode 2 of either: no weight gradient is contracted or reduced, the gradient buffer is left alone, and
+ * ntx_trainer_adam_step, ntx_trainer_allreduce_gradients and ntx_trainer_stash_gradients return NTX_E_INVALID.  A change of either mode drops
+ * a pending ntx_train_forward (its ntx_train_backward returns NTX_E_INVALID): set the modes before the forward.
+ * Checked before anything is placed, and a failed call leaves both modes as they were: NTX_E_INVALID for t NULL, a mode outside 0..2, or
+ * param_mode != 0 on a model without parameters; NTX_E_UNSUPPORTED for a non-zero mode on an IPE chain handle (the cone gaussians' derivative
+ * is not written).  ntx_trainer_enable_param_gradients and ntx_trainer_enable_input_gradients keep refusing a chain handle.
+ * Out of scope on the chain: an instanced step (refused as before), IPE models, depths / tnear_far / cone_scale, an all-reduce of these
+ * gradients, second order. */
+int ntx_trainer_enable_gradients(ntx_trainer *t, int param_mode, int input_mode);
 
 #ifdef __cplusplus
 }

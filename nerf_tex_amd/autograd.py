@@ -8,10 +8,10 @@
 
 Every gradient of a step is linear in dL/d color_pred and dL/d alpha_pred, so autograd only has to hand those two cotangents to
 `Trainer.backward` (`ntx_train_backward`, include/nerftex.h): the weight gradient is left in the trainer as `gradients_step` leaves it
-(`gradients()`, `sync_gradients`, `apply_gradients`), and -- with `param_gradients=True` / "only" on a layer-by-layer trainer and
-`parameters.requires_grad` -- dL/d parameters flows on into `parameters.grad` [rows, P], where other torch terms on `parameters` add up.
+(`gradients()`, `sync_gradients`, `apply_gradients`), and -- with `param_gradients=True` / "only" on the trainer (a layer-by-layer one, or the fused
+chain: `Trainer(..., param_gradients=)`) and `parameters.requires_grad` -- dL/d parameters flows on into `parameters.grad` [rows, P], where other torch terms on `parameters` add up.
 
-With `input_gradients=True` / "only" on a layer-by-layer trainer, `rays_o` / `rays_d` that require grad receive dL/d rays_o and dL/d rays_d
+With `input_gradients=True` / "only" on the trainer (either kind), `rays_o` / `rays_d` that require grad receive dL/d rays_o and dL/d rays_d
 likewise (camera or pose refinement: the sample depths are constants), and the instanced op's `pts` / `rays_d_map` theirs; with it off, both ops
 do what they do without it.
 

@@ -7,6 +7,8 @@
 //   encode_kernel   sample points and the encodings of position / direction / parameters (ntx_encode.h): the first layer's and the two
 //                   concatenations' inputs, in the row order the chain reads and in the operand order the weight gradients read
 //   dirrow_kernel   the colour layer's direction segment once per ray, where a ray's samples share it
+//   feat_grad_kernel  where dL/d params or dL/d rays is asked for (ntx_trainer_enable_gradients): the gradient at pos_map and dir_map, the three
+//                   products the chain back leaves out, on the f32 matrix cores; ntx_backend_flex.hip's folds take it from there
 // The handle, the composite, the loss, the partial sums' reduction and Adam are ntx_trainer.hip's.  gfx950 only.
 #include <algorithm>
 #include <cstdio>
@@ -148,6 +150,82 @@ __global__ __launch_bounds__(256) void dirrow_kernel(DirRowArgs a) {
     a.rows[(size_t)ray * 256 + h * 128 + 16 * T + 4 * g + c] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The gradient at the encoded inputs (ntx_trainer_enable_gradients): the three products the chain back leaves out -- dX of trunk layer 0, the
+// skip layer's pos_map rows, C1's dir_map rows --
+//     G[m][j] = sum over the terms (dY, W) of sum_o dY[m][o] W[j][o],     j < K
+// G_pos: (dy0, W_trunk0), (dy5, W_trunk5), K = Kp;  G_dir: (dc1o, W_c1), K = Kd.  dY: the kept O-layout gradients (256 rows), W: the first K
+// rows of the layer's kernel in the Keras-order blob, row j contiguous over o.  Output row-major [M][ld], ld = K padded to 4 (the padding
+// columns are written as zeros): what flex_param_fold_kernel / flex_ray_fold_kernel read.
+// A wave per block of 32 samples on v_mfma_f32_32x32x2_f32, transposed like the chains: G^T[j, sample] = W[j, o] . dY^T[o, sample], NT tiles
+// of 32 rows j.  A operand: lane (j, kh) loads 16 bytes W[j][8 q + 4 kh + (0..3)] = four k-steps; B operand: lane (n, kh) gathers dwords
+// dY[row 8 q + 4 kh + c][sample n] of the O-layout block -- the very addresses dx_chain_kernel's lane (n, kh) stored its value V = 4 q + c
+// to (o_lane_bytes + o_value_bytes).  Rows j >= K lie beyond the weight resource's end and read as 0.  D of a tile: lane (n, h) holds rows
+// 8 g + 4 h + (0..3) in registers 4 g .. 4 g + 3: four consecutive j of sample n, one 16-byte store.  Rows m >= M are not written.
+// The order of a sum: from 0, the terms in the order given, within a term k-step V = 0 .. 127 ascending, within a k-step feature
+// hidden_row(V, 0) then hidden_row(V, 1) (the MFMA's k = 0, 1): one fmaf chain per output, whatever the grid and the trainer's capacity.
+// No atomics.  The grid is persistent (ChainBackend::feat_grid): wave w takes the blocks w, w + n_waves, ...
+// ---------------------------------------------------------------------------------------------------------------------------
+struct FeatGradArgs {
+    const float *dY[2], *W[2]; int n_terms;   // a term's dY: O layout, 8 tiles a block; W: [K][256]
+    int K, ld; long long M;
+    float *G;                                  // [M][ld]
+};
+template <int NT>
+__global__ __launch_bounds__(256) void feat_grad_kernel(FeatGradArgs a) {
+    const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), nwaves = gridDim.x * 4;
+    const int n_blocks = (int)((a.M + 31) >> 5);
+    const uint32_t voff_y = o_lane_bytes(lane);
+    uint32_t voff_w[NT];
+    static_for<NT>([&](auto T) { constexpr int t = T; voff_w[t] = (uint32_t)(32 * t + n) * 1024u + (uint32_t)h * 16u; });
+    for (int blk = wave; blk < n_blocks; blk += nwaves) {
+        f32x16 acc[NT];
+        static_for<NT>([&](auto T) { acc[T] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; });
+        for (int term = 0; term < a.n_terms; ++term) {
+            const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.W[term], (long long)a.K * 1024);
+            const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.dY[term] + (size_t)blk * 8 * 1024, 8 * 4096);
+            // groups of four 16-byte steps (16 k-steps = one tile of dY's rows), one group ahead of the MFMAs
+            f32x4 wa[2][4][NT]; float yb[2][16];
+            auto fetch = [&](auto BUF, int grp) {
+                constexpr int buf = BUF;
+                static_for<4>([&](auto Q) {
+                    constexpr int q = Q;
+                    static_for<NT>([&](auto T) {
+                        wa[buf][q][T] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, voff_w[T], (uint32_t)(4 * grp + q) * 32u, 0)); });
+                    static_for<4>([&](auto Cc) {
+                        constexpr int c = Cc;
+                        yb[buf][4 * q + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, voff_y, (uint32_t)grp * 4096u + o_value_bytes(4 * q + c), 0)); });
+                });
+            };
+            auto compute = [&](auto BUF) {
+                constexpr int buf = BUF;
+                static_for<4>([&](auto Q) { static_for<4>([&](auto Cc) { static_for<NT>([&](auto T) {
+                    constexpr int q = Q, c = Cc;
+                    acc[T] = mfma32(wa[buf][q][T][c], yb[buf][4 * q + c], acc[T]);
+                }); }); });
+            };
+            // (unconditional fetches, as in dw_piece: behind the last group it is asked for again and not used)
+            fetch(std::integral_constant<int, 0>{}, 0);
+            for (int grp = 0; grp < 8; grp += 2) {
+                fetch(std::integral_constant<int, 1>{}, grp + 1);
+                compute(std::integral_constant<int, 0>{});
+                fetch(std::integral_constant<int, 0>{}, grp + 2 < 8 ? grp + 2 : grp + 1);
+                compute(std::integral_constant<int, 1>{});
+            }
+        }
+        const long long m = (long long)blk * 32 + n;
+        if (m < a.M) {
+            float *row = a.G + (size_t)m * a.ld;
+            static_for<NT>([&](auto T) { static_for<4>([&](auto Gq) {
+                constexpr int t = T, g = Gq;
+                const int j = 32 * t + 8 * g + 4 * h;
+                if (j < a.ld) *reinterpret_cast<f32x4 *>(row + j) = f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+            }); });
+        }
+    }
+}
+
 }   // namespace ntx_train
 namespace {
 using namespace ntx_train;
@@ -165,14 +243,20 @@ struct ChainBackend : Backend {
     DwJob *jobs = nullptr; int n_jobs = 0; long long total_cost = 0;      // the weight gradients' jobs (ntx_train_device.h), their costs per block added up
     std::vector<DwJob> jobs_host; std::vector<int> reduce_job;      // reduce_job[i]: the job whose slots reduction i adds up
     float *dw_partial = nullptr; ReduceBatch reduce{};     // (n_split per step)
+    float *G_pos = nullptr, *G_dir = nullptr; int ld_pos = 0, ld_dir = 0;      // ntx_trainer_enable_gradients: the gradient at pos_map / dir_map [cap][pad4(Kp / Kd)] (feat_grad_kernel)
+    float *ray_pg = nullptr;                   // [cap_rays][P]: a ray's samples folded and added
     float *act_at(int i) const { return act + (size_t)i * act_stride; }
     float *gout_at(int i) const { return gout + (size_t)i * gout_stride; }
     unsigned chain_grid(const StepRays &r) const { return (unsigned)std::min<long long>(t->cus, (r.n_blocks() + 3) / 4); }      // persistent: a workgroup of four waves per CU
+    unsigned feat_grid(const StepRays &r) const { return (unsigned)std::min<long long>(2 * (long long)t->cus, (r.n_blocks() + 3) / 4); }   // persistent: two workgroups of four waves per CU
     size_t plan_layers(const ntx_model_desc &d, bool ipe);
     void build_pack();
     void build_dw_jobs();
     int forward(const StepRays &r, hipStream_t st) override;
     int backward(const StepRays &r, hipStream_t st) override;
+    void backward_weights(int n_blocks, hipStream_t st);
+    int enable_gradients(int param_mode, int input_mode) override;
+    void launch_feat_grad(hipStream_t st, unsigned grid, int tiles, const FeatGradArgs &a);
     int activation(int layer, int64_t n_samples_total, float *out_host) override;
 };
 
@@ -378,6 +462,23 @@ int ChainBackend::backward(const StepRays &r, hipStream_t st) {
     DxArgs x{}; x.stream = wdx; x.stream_bytes = (uint32_t)(dx_floats * sizeof(float)); x.M = r.M(); x.dgrad = t->dgrad;
     x.out = gout; x.out_stride = gout_stride; x.bits = bits; x.bits_stride = bits_stride;
     launch_dx_chain(st, chain_grid(r), x);
+    if (t->pg_mode != 0 || t->ig_mode != 0) {                                // the gradient at pos_map and at dir_map, all Kp / Kd columns whichever mode asked
+        FeatGradArgs p{}; p.dY[0] = gout_at(10); p.W[0] = t->w + trunk[0].w; p.dY[1] = gout_at(5); p.W[1] = t->w + trunk[5].w; p.n_terms = 2;
+        p.K = t->Kp; p.ld = ld_pos; p.M = r.M(); p.G = G_pos;
+        launch_feat_grad(st, feat_grid(r), ptiles, p);
+        FeatGradArgs d{}; d.dY[0] = gout_at(1); d.W[0] = t->w + c1.w; d.n_terms = 1; d.K = t->Kd; d.ld = ld_dir; d.M = r.M(); d.G = G_dir;
+        launch_feat_grad(st, feat_grid(r), dtiles, d);
+    }
+    if (t->takes_weight_gradients()) backward_weights(n_blocks, st);         // either mode 2: no weight gradient is taken or reduced
+    // the folds of the layer-by-layer backend: the parameter features' and the FF(xyz) / FF(dir) rows' gradient through the encoder
+    if (t->pg_mode != 0) {
+        const ntx_model_desc &m = t->desc;
+        launch_param_fold(st, r, G_pos + 3 * (1 + 2 * m.pos_freq), G_dir + 3 * (1 + 2 * m.dir_freq), ld_pos, ld_dir, ray_pg, t->P, t->param_grad);
+    }
+    if (t->ig_mode != 0) launch_ray_fold(st, r, G_pos, G_dir, ld_pos, ld_dir, t->dgrad, t->sigma, t->step_noise, t->d_rays_o, t->d_rays_d);
+    return NTX_OK;
+}
+void ChainBackend::backward_weights(int n_blocks, hipStream_t st) {
     // every layer's dW = X^T . dY and db = the column sums of dY in one launch of one workgroup per CU, each with an equal share of the work ...
     DwArgs d{}; d.jobs = jobs; d.n_jobs = n_jobs; d.n_blocks = n_blocks; d.total_cost = total_cost; d.partial = dw_partial;
     const long long G = t->cus, W = total_cost * n_blocks;
@@ -399,7 +500,28 @@ int ChainBackend::backward(const StepRays &r, hipStream_t st) {
     }
     for (int i = 0; i < rb.n; ++i) rb.job[i].n_split = slots[reduce_job[i]];
     launch_reduce(st, rb);
-    return NTX_OK;
+}
+
+void ChainBackend::launch_feat_grad(hipStream_t st, unsigned grid, int tiles, const FeatGradArgs &a) {
+    if (tiles <= 1) hipLaunchKernelGGL(feat_grad_kernel<1>, dim3(grid), dim3(256), 0, st, a);
+    else if (tiles == 2) hipLaunchKernelGGL(feat_grad_kernel<2>, dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(feat_grad_kernel<3>, dim3(grid), dim3(256), 0, st, a);
+}
+
+// What dL/d params and dL/d rays need on the chain, placed at the first enable for the trainer's capacity: the gradient at the encoded
+// inputs, a ray's and a row's parameter sums, the two ray results.  A handle that never enables anything has none of it
+int ChainBackend::enable_gradients(int param_mode, int input_mode) {
+    if (param_mode == 0 && input_mode == 0) return NTX_OK;
+    if (t->ipe) return ntx_set_error(NTX_E_UNSUPPORTED, "parameter / input gradients of an IPE model on the fused chain: the cone gaussians' derivative is not written");
+    if (G_pos) return NTX_OK;
+    DeviceMemory &mem = t->mem;
+    TRAIN_TRY(hipSetDevice(t->device));
+    ld_pos = pad4(t->Kp); ld_dir = pad4(t->Kd);
+    mem.alloc(&G_dir, (size_t)t->cap * ld_dir);
+    mem.alloc(&ray_pg, (size_t)t->cap_rays * t->P); mem.alloc(&t->param_grad, (size_t)t->cap_rays * t->P);
+    mem.alloc(&t->d_rays_o, (size_t)t->cap_rays * 3); mem.alloc(&t->d_rays_d, (size_t)t->cap_rays * 3);
+    mem.alloc(&G_pos, (size_t)t->cap * ld_pos);                              // (last: it is the mark that all of it is placed)
+    return mem.rc;
 }
 
 int ChainBackend::activation(int layer, int64_t n_samples_total, float *out_host) {
@@ -413,9 +535,16 @@ int ChainBackend::activation(int layer, int64_t n_samples_total, float *out_host
     else if (layer == 29) src = gout_at(2);
     else if (layer == 11) src = t->raw_rgb;
     else if (layer == 30) src = t->dgrad;
-    else return ntx_set_error(NTX_E_INVALID, "layer %d (0-7 trunk, 8 / 9 the colour layers, 10 the density, 11 the raw colour; 20-29 the kept gradients, 30 the composite's adjoint)", layer);
+    else if ((layer == 40 || layer == 41) && G_pos && ((t->pg_mode != 0 && t->pg_rows > 0) || (t->ig_mode != 0 && t->ig_rays > 0))) src = layer == 40 ? G_pos : G_dir;
+    else return ntx_set_error(NTX_E_INVALID, "layer %d (0-7 trunk, 8 / 9 the colour layers, 10 the density, 11 the raw colour; 20-29 the kept gradients, 30 the composite's adjoint; "
+                              "40 / 41 the gradient at pos_map / dir_map of a step under ntx_trainer_enable_gradients)", layer);
     TRAIN_TRY(hipSetDevice(t->device));
     TRAIN_TRY(hipDeviceSynchronize());
+    if (layer == 40 || layer == 41) {                                        // row-major [n][pad4(K)] -> [n][K]
+        const int K = layer == 40 ? t->Kp : t->Kd, ld = layer == 40 ? ld_pos : ld_dir;
+        TRAIN_TRY(hipMemcpy2D(out_host, (size_t)K * sizeof(float), src, (size_t)ld * sizeof(float), (size_t)K * sizeof(float), (size_t)n_samples_total, hipMemcpyDeviceToHost));
+        return NTX_OK;
+    }
     if (layer == 10 || layer == 11 || layer == 30) {
         const size_t width = layer == 10 ? 1 : (layer == 11 ? 3 : 4);
         TRAIN_TRY(hipMemcpy(out_host, src, (size_t)n_samples_total * width * sizeof(float), hipMemcpyDeviceToHost)); return NTX_OK;

@@ -365,7 +365,6 @@ struct FlexBranch {
     bool exists() const { return !layers.empty(); }
 };
 
-inline int pad4(int n) { return (n + 3) & ~3; }
 struct FlexBackend : Backend {
     ntx_trainer *t = nullptr;
     std::vector<FlexLayer> layers;
@@ -678,18 +677,10 @@ void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split,
 
 int FlexBackend::backward(const StepRays &r, hipStream_t st) {
     network_backward(r.M(), st);
-    if (t->pg_mode != 0) {                                                   // the features' gradient through the encoder, a ray's samples, a row's rays
-        const int P = t->P;
-        const long long rows = (r.n_rays + r.rays_per_param_row - 1) / r.rays_per_param_row;
-        FlexFoldArgs f{}; f.r = r; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.ray_pg = ray_pg;
-        hipLaunchKernelGGL(flex_param_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
-        hipLaunchKernelGGL(flex_param_rows_kernel, dim3((unsigned)((rows * P + 255) / 256)), dim3(256), 0, st, ray_pg, r.n_rays, r.rays_per_param_row, P, rows, t->param_grad);
-    }
-    if (t->ig_mode != 0) {                                                   // the FF(xyz) / FF(dir) rows' gradient through the encoder, a ray's samples
-        FlexRayFoldArgs f{}; f.r = r; f.ig_pos = IG[0]; f.ig_dir = IG[1]; f.ld_pos = ldig[0]; f.ld_dir = ldig[1]; f.dgrad = t->dgrad; f.sigma = t->sigma;
-        f.noise = t->step_noise; f.d_rays_o = t->d_rays_o; f.d_rays_d = t->d_rays_d;
-        hipLaunchKernelGGL(flex_ray_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
-    }
+    // the features' gradient through the encoder, a ray's samples, a row's rays
+    if (t->pg_mode != 0) launch_param_fold(st, r, PG[0], PG[1], ldpg[0], ldpg[1], ray_pg, t->P, t->param_grad);
+    // the FF(xyz) / FF(dir) rows' gradient through the encoder, a ray's samples
+    if (t->ig_mode != 0) launch_ray_fold(st, r, IG[0], IG[1], ldig[0], ldig[1], t->dgrad, t->sigma, t->step_noise, t->d_rays_o, t->d_rays_d);
     return NTX_OK;
 }
 // An instanced step's way back over its n_live rows.  Without a live sample nothing is contracted: every weight gradient is exactly 0 (mode
@@ -819,6 +810,19 @@ int flex_check(const ntx_model_desc *desc, TrainDims *dims, bool branches) {
     dims->n_weights = plan.plan(desc, pd, pw);
     dims->Kp = plan.Kp; dims->Kd = plan.Kd;
     return NTX_OK;
+}
+
+void launch_param_fold(hipStream_t st, const StepRays &r, const float *pg_geo, const float *pg_app, int ld_geo, int ld_app, float *ray_pg, int P, float *param_grad) {
+    const long long rows = (r.n_rays + r.rays_per_param_row - 1) / r.rays_per_param_row;
+    FlexFoldArgs f{}; f.r = r; f.pg_geo = pg_geo; f.pg_app = pg_app; f.ld_geo = ld_geo; f.ld_app = ld_app; f.ray_pg = ray_pg;
+    hipLaunchKernelGGL(flex_param_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
+    hipLaunchKernelGGL(flex_param_rows_kernel, dim3((unsigned)((rows * P + 255) / 256)), dim3(256), 0, st, ray_pg, r.n_rays, r.rays_per_param_row, P, rows, param_grad);
+}
+void launch_ray_fold(hipStream_t st, const StepRays &r, const float *ig_pos, const float *ig_dir, int ld_pos, int ld_dir, const float *dgrad, const float *sigma,
+                     const float *noise, float *d_rays_o, float *d_rays_d) {
+    FlexRayFoldArgs f{}; f.r = r; f.ig_pos = ig_pos; f.ig_dir = ig_dir; f.ld_pos = ld_pos; f.ld_dir = ld_dir; f.dgrad = dgrad; f.sigma = sigma;
+    f.noise = noise; f.d_rays_o = d_rays_o; f.d_rays_d = d_rays_d;
+    hipLaunchKernelGGL(flex_ray_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
 }
 
 int flex_backend_create(ntx_trainer *t) {

@@ -86,6 +86,12 @@ struct Backend {
         return ntx_set_error(NTX_E_UNSUPPORTED, "input gradients: the fused chain (ntx_trainer_create) stops at the encoded inputs; the layer-by-layer "
                              "trainer takes the same model (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
     }
+    // ntx_trainer_enable_gradients, both modes at once and checked (0 .. 2; param_mode 0 on a model without parameters): places what the
+    // non-zero ones need (once) and refuses before anything is placed; the handle keeps the modes.  The chain's way in
+    virtual int enable_gradients(int param_mode, int input_mode) {
+        if (param_mode != 0) { const int rc = enable_param_gradients(); if (rc != NTX_OK) return rc; }
+        return input_mode != 0 ? enable_input_gradients() : NTX_OK;
+    }
 };
 // what an entry's architecture check makes of a descriptor
 struct TrainDims { ntx_model_desc desc; int Kp, Kd; bool ipe; size_t n_weights; int param_depth, param_width; };   // param_*: the branches the model HAS (0 without parameters)
@@ -155,5 +161,12 @@ constexpr int MAX_REDUCE_BATCH = 32;
 struct ReduceJob { const float *partial; int n_split; long long stride, count, pair; float *out; long long first; };   // pair > 0: element e of a split is partial[e] + partial[pair + e]
 struct ReduceBatch { ReduceJob job[MAX_REDUCE_BATCH]; int n; };
 void launch_reduce(hipStream_t st, const ReduceBatch &b);
+// ntx_backend_flex.hip: the two folds behind the gradient at the encoded inputs (flex_param_fold_kernel + flex_param_rows_kernel;
+// flex_ray_fold_kernel), for both backends.  pg_geo / pg_app: the gradient at the geometry / appearance parameter features of every sample, rows
+// of ld_geo / ld_app floats; ig_pos / ig_dir: at the FF(xyz) / FF(dir) rows
+void launch_param_fold(hipStream_t st, const StepRays &r, const float *pg_geo, const float *pg_app, int ld_geo, int ld_app, float *ray_pg, int P, float *param_grad);
+void launch_ray_fold(hipStream_t st, const StepRays &r, const float *ig_pos, const float *ig_dir, int ld_pos, int ld_dir, const float *dgrad, const float *sigma,
+                     const float *noise, float *d_rays_o, float *d_rays_d);
+inline int pad4(int n) { return (n + 3) & ~3; }      // a row of n floats padded to 16 bytes
 __device__ __forceinline__ float wave_sumf(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
 }   // namespace ntx_train

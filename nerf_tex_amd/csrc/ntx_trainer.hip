@@ -783,6 +783,20 @@ int ntx_trainer_enable_input_gradients(ntx_trainer *t, int mode) {
     return NTX_OK;
 }
 
+int ntx_trainer_enable_gradients(ntx_trainer *t, int param_mode, int input_mode) {
+    if (!t || param_mode < 0 || param_mode > 2 || input_mode < 0 || input_mode > 2)
+        return ntx_set_error(NTX_E_INVALID, "trainer is NULL or a mode is not 0 (off) / 1 (beside the weight gradients) / 2 (without them)");
+    if (param_mode != 0 && t->P == 0)
+        return ntx_set_error(NTX_E_INVALID, "parameter gradients: the model has no parameters (a Nerf, n_parameters [0, 0])");
+    int rc = t->backend->enable_gradients(param_mode, input_mode);              // refuses before it places anything; places once
+    if (rc != NTX_OK) return rc;
+    if (param_mode == 0) { t->pg_rows = 0; t->spg_rays = 0; }
+    if (input_mode == 0) { t->ig_rays = 0; t->ig_smp_rays = 0; }
+    if (param_mode != t->pg_mode || input_mode != t->ig_mode) t->pending.open = false;      // set the modes before the forward
+    t->pg_mode = param_mode; t->ig_mode = input_mode;
+    return NTX_OK;
+}
+
 int ntx_trainer_ray_gradients(ntx_trainer *t, const float **d_rays_o, const float **d_rays_d, int64_t *n_rays) {
     if (!t || !d_rays_o || !d_rays_d || !n_rays) return ntx_set_error(NTX_E_INVALID, "NULL argument");
     if (t->ig_mode == 0 || t->ig_rays == 0) return ntx_set_error(NTX_E_INVALID, "no ray gradients: %s", t->ig_mode == 0 ? "ntx_trainer_enable_input_gradients is off" :

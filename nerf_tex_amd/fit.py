@@ -6,8 +6,9 @@ target images it finds the parameters that reproduce them, by gradient descent o
     params, history = fitter.fit(batch, AlphaLoss(...), init=[[0.5] * 5] * 2, n_iters=200)
 
 The gradient is the layer-by-layer trainer's dL/d parameters in its parameters-only mode (`ntx_trainer_enable_param_gradients` mode 2: the
-forward pass, the composite's adjoint and the way back through the activations, no weight gradient); the update of the handful of
-parameters is `torch.optim.Adam` on the device.  Positions and directions take no gradient; an IPE model and a coarse + fine pair are not
+forward pass, the composite's adjoint and the way back through the activations, no weight gradient) -- or, with `fused=True` and a model of the
+fused chain's 8 x 256 shape, the chain's (`ntx_trainer_enable_gradients`); the update of the handful of parameters is `torch.optim.Adam` on the
+device.  Positions and directions take no gradient; an IPE model and a coarse + fine pair are not
 taken.  `loss`: a `nerf_tex_amd.loss` object, or any callable `loss(color_true=, alpha_true=, color_pred=, alpha_pred=)` on torch tensors that
 returns a scalar -- a robust loss for photographs, say (`Trainer.gradients_step`)."""
 
@@ -18,17 +19,18 @@ from typing import Optional
 
 class ParameterFitter:
     def __init__(self, model, n_samples: int, max_rays: int, blur_idx: Optional[int] = None, perturb: bool = False, raw_noise_std: float = 0, map_exr: bool = False,
-                 lrate: float = 1e-2, bounds=None, device: int = 0) -> None:
+                 lrate: float = 1e-2, bounds=None, device: int = 0, fused: bool = False) -> None:
         """`model`: the trained Nerf-Tex (`nerf_tex_amd.model.ParamNerf` container; its blob gives the weights, which never change);
         `n_samples`, `blur_idx`, `perturb`, `raw_noise_std`, `map_exr`: the renderer's, as the model was trained; `max_rays`: the largest batch
         (images x rays per image); `lrate`: Adam's; `bounds`: None or (low, high), scalars or one value per parameter -- the parameters are
-        clamped to them after every update."""
+        clamped to them after every update; `fused`: an 8 x 256 / skips [4] / color_depth 1 FourierFeatures model keeps the fused chain
+        (`trainer_for(..., fused=True)`), every other model trains layer by layer as without it."""
         from .train import trainer_for
         if getattr(model, "n_params", 0) < 1:
             raise ValueError("the model has no parameters to fit (a Nerf, or n_parameters [0, 0])")
         self.model, self.lrate, self.bounds, self.device = model, float(lrate), bounds, int(device)
         self.trainer = trainer_for(model, param_gradients="only", max_rays=int(max_rays), n_samples=int(n_samples), blur_idx=blur_idx, perturb=perturb,
-                                   raw_noise_std=raw_noise_std, map_exr=map_exr, device=device)
+                                   raw_noise_std=raw_noise_std, map_exr=map_exr, device=device, fused=fused)
 
     def step(self, batch: dict, loss, parameters, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.), seed: Optional[int] = None):
         """The loss of `batch` at `parameters` [B, P] and its gradient [B, P] (GPU tensors): `batch` as `Train` takes it -- rays_o / rays_d

@@ -18,7 +18,9 @@ contraction per Dense layer and pass (`ntx_trainer_create_flex`); `BranchTrainer
 (param_depth 1..4, param_width 2..128: `ntx_trainer_create_flex_ex`).  `trainer_for(model, ...)` picks between them, and
 `Trainer.from_config`, `CoarseFineTrainer` and `Train` build their trainers through it.  The layer-by-layer trainers also take the one
 gradient a training step otherwise leaves out, dL/d material parameters (`param_gradients=`, `parameter_gradients()`); `nerf_tex_amd.fit`
-fits parameters to target images with it.  The losses of `nerf_tex_amd.loss` are evaluated inside the step; any other loss is a callable on
+fits parameters to target images with it.  The fused chain takes the same two keywords for a FourierFeatures model (`set_gradients`,
+`ntx_trainer_enable_gradients`), and `trainer_for(model, ..., fused=True)` keeps such a model on it when a gradient is asked for.
+The losses of `nerf_tex_amd.loss` are evaluated inside the step; any other loss is a callable on
 torch tensors, and the step runs as `forward(...)`, the loss and its two cotangents in torch, `backward(d_color, d_alpha)`
 (`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op).  The layer-by-layer trainers also take the step through
 the INSTANCED render (`forward_instanced(bufs, ...)` on an instancer's buffers, then the same `backward`; `DifferentiableInstanceRender`)."""
@@ -33,13 +35,15 @@ from . import _lib
 
 class Trainer:
     def __init__(self, model, max_rays: int, n_samples: int, lrate: float = 5e-4, lrate_decay: float = 0, perturb: bool = True, blur_idx: Optional[int] = None,
-                 map_exr: bool = False, raw_noise_std: float = 0.0, beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, device: int = 0) -> None:
+                 map_exr: bool = False, raw_noise_std: float = 0.0, beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, device: int = 0,
+                 param_gradients=False, input_gradients=False) -> None:
         """`model`: a nerf_tex_amd.model.ParamNerf container (its blob gives the initial weights); `lrate`, `lrate_decay` as train.py:49-50
         (ExponentialDecay(lrate, decay_steps=lrate_decay * 1e3, decay_rate=0.1) when lrate_decay > 0); `perturb`, `blur_idx`, `map_exr`: the
         renderer's (renderer.py:34); `raw_noise_std`: the density regulariser of map_model_output (renderer.py:190-192; config_grass_filtered_train.py:99
         trains with 0.1), drawn per (seed, ray, sample) like the jitter.  An IPE model (pos_encoding 'ipe', n_pos 6) trains as the MipRenderer
         renders it (renderer.py:365-444): `n_samples` cone segments between n_samples + 1 depths, the parameter rows hold the blur parameter at
-        `blur_idx` (required) -- its product with cone_scale is the cone's radius, and the model sees the other parameters."""
+        `blur_idx` (required) -- its product with cone_scale is the cone's radius, and the model sees the other parameters.
+        `param_gradients` / `input_gradients`: False, True or "only" (`set_gradients`), for a FourierFeatures model."""
         import numpy as np
         self.mip = getattr(model, "pos_encoding", "fourier") == "ipe"
         if self.mip and blur_idx is None:
@@ -69,6 +73,9 @@ class Trainer:
         self._calls = 0
         self._last_rays = 0
         self._pending, self._forwards = None, 0                                 # (serial, rays, device tensors) of a `forward` whose `backward` has not run
+        self.param_gradients = self.input_gradients = False
+        if param_gradients is not False or input_gradients is not False:
+            self.set_gradients(param_gradients, input_gradients)
 
     _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create(*a))           # the entry that makes the native trainer
     _widen = staticmethod(lambda model: _widened(model))                           # a narrower network inside the 256-wide one
@@ -133,12 +140,12 @@ class Trainer:
     def activation(self, layer: int, n_samples_total: int):
         """What the last step kept of layer 0-7 (trunk), 8 / 9 (colour layers), 10 (raw density), 11 (raw colour), or -- 20-27, 28, 29 -- the
         gradient at the outputs of the trunk layers, the first colour layer, the feature layer, 30 the composite's adjoint (dL/d raw colour,
-        dL/d raw density): [n_samples_total, width] float32 (tests)."""
+        dL/d raw density), 40 / 41 the gradient at pos_map / dir_map of a step under `set_gradients`: [n_samples_total, width] float32 (tests)."""
         import numpy as np
-        width = {9: 128, 10: 1, 11: 3, 30: 4}.get(int(layer), 256)
+        width = {9: 128, 10: 1, 11: 3, 30: 4, 40: self.model.pos_map_dim, 41: self.model.dir_map_dim}.get(int(layer), 256)
         out = np.empty((int(n_samples_total), width), np.float32)
         _lib.check(_lib.lib.ntx_trainer_activation(self._h, int(layer), int(n_samples_total), out.ctypes.data_as(C.POINTER(C.c_float))))
-        if self._pad is not None and width > 4:                                 # the narrow network's own columns
+        if self._pad is not None and width > 4 and int(layer) < 40:             # the narrow network's own columns
             out = np.ascontiguousarray(out[:, :self.model.width // (2 if layer == 9 else 1)])
         return out
 
@@ -320,6 +327,53 @@ class Trainer:
         self.backward(torch.zeros_like(color) if d_color is None else d_color, d_alpha)
         return val.detach().reshape(1), color, alpha
 
+    def set_gradients(self, param_gradients=False, input_gradients=False) -> None:
+        """Both gradient modes for the following steps, each False / True / "only" (`ntx_trainer_enable_gradients`; the buffers are placed
+        at the first True or "only"): True -- every step also leaves dL/d parameters (`parameter_gradients()`) or dL/d rays_o, rays_d
+        (`ray_gradients()`), loss, predictions and weight gradients bit for bit as without it; "only" -- the same gradients and no weight
+        gradient at all (`gradients()` keeps what it held; `apply_gradients` raises NTX_E_INVALID) while either is "only".  On the fused chain
+        for a FourierFeatures model (an IPE model: NTX_E_UNSUPPORTED); set them before a `forward`, a change drops the pending one."""
+        modes = {False: 0, True: 1, "only": 2}
+        native = []
+        for name, mode in (("param_gradients", param_gradients), ("input_gradients", input_gradients)):
+            if not (isinstance(mode, (int, str)) and mode in modes):
+                raise ValueError(f'{name} must be False, True or "only", not {mode!r}')
+            native.append(modes[mode])
+        import torch
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.ntx_trainer_enable_gradients(self._h, native[0], native[1]))
+        self.param_gradients, self.input_gradients = ("only" if m == 2 else bool(m) for m in native)
+
+    def _device_copies(self, ptrs, shape):
+        """Copies of the trainer's device results `ptrs` as torch tensors of `shape`, in the current stream's order."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        outs = tuple(torch.empty(shape, device=dev, dtype=torch.float32) for _ in ptrs)
+        with torch.cuda.device(dev):
+            for out, ptr in zip(outs, ptrs):
+                if out.numel():
+                    _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
+        return outs
+
+    def ray_gradients(self):
+        """(dL/d rays_o, dL/d rays_d) of the last plain step: torch tensors [N, 3] on the trainer's device, copies in the current stream's
+        order.  The sample depths are constants; a ray that misses has exact zeros."""
+        o, d, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        _lib.check(_lib.lib.ntx_trainer_ray_gradients(self._h, C.byref(o), C.byref(d), C.byref(n)))
+        return self._device_copies((o, d), (int(n.value), 3))
+
+    def parameter_gradients(self):
+        """dL/d parameters of the last step: a torch tensor [rows, P] on the trainer's device (rows = the step's parameter rows,
+        ceil(n_rays / rays_per_param_row); geometry columns first), a copy in the current stream's order."""
+        import torch
+        ptr, rows, n = C.c_void_p(), C.c_int64(), C.c_int()
+        _lib.check(_lib.lib.ntx_trainer_param_gradients(self._h, C.byref(ptr), C.byref(rows), C.byref(n)))
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((int(rows.value), int(n.value)), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
     def apply_gradients(self) -> None:
         """optimizer.apply_gradients (train.py:67): Adam under the learning-rate schedule of train.py:49-52."""
         import torch
@@ -427,42 +481,12 @@ class FlexTrainer(Trainer):
             _lib.check(_lib.lib.ntx_trainer_enable_input_gradients(self._h, native))
         self.input_gradients = "only" if native == 2 else bool(native)
 
-    def _device_copies(self, ptrs, shape):
-        """Copies of the trainer's device results `ptrs` as torch tensors of `shape`, in the current stream's order."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        outs = tuple(torch.empty(shape, device=dev, dtype=torch.float32) for _ in ptrs)
-        with torch.cuda.device(dev):
-            for out, ptr in zip(outs, ptrs):
-                if out.numel():
-                    _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
-        return outs
-
-    def ray_gradients(self):
-        """(dL/d rays_o, dL/d rays_d) of the last plain step: torch tensors [N, 3] on the trainer's device, copies in the current stream's
-        order.  The sample depths are constants; a ray that misses has exact zeros."""
-        o, d, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        _lib.check(_lib.lib.ntx_trainer_ray_gradients(self._h, C.byref(o), C.byref(d), C.byref(n)))
-        return self._device_copies((o, d), (int(n.value), 3))
-
     def sample_input_gradients(self):
         """(dL/d pts, dL/d rays_d_map) of the last INSTANCED step: torch tensors [N, S, 3] on the trainer's device (exact zeros at samples
         outside every patch), copies in the current stream's order."""
         p, d, n, s = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int()
         _lib.check(_lib.lib.ntx_trainer_sample_input_gradients(self._h, C.byref(p), C.byref(d), C.byref(n), C.byref(s)))
         return self._device_copies((p, d), (int(n.value), int(s.value), 3))
-
-    def parameter_gradients(self):
-        """dL/d parameters of the last step: a torch tensor [rows, P] on the trainer's device (rows = the step's parameter rows,
-        ceil(n_rays / rays_per_param_row); geometry columns first), a copy in the current stream's order."""
-        import torch
-        ptr, rows, n = C.c_void_p(), C.c_int64(), C.c_int()
-        _lib.check(_lib.lib.ntx_trainer_param_gradients(self._h, C.byref(ptr), C.byref(rows), C.byref(n)))
-        dev = torch.device("cuda", self.device)
-        out = torch.empty((int(rows.value), int(n.value)), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
-        return out
 
     def forward_instanced(self, bufs, cone_scale, *, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True, composite_bkgd: bool = False,
                           bkgd_color=(1., 1., 1.), hit=None):
@@ -581,14 +605,19 @@ def _chain_takes(model) -> bool:
     return _widened(model) is not None and model.n_pos == 3
 
 
-def trainer_class_for(model, branches: bool = False, param_gradients=False, input_gradients=False):
+def trainer_class_for(model, branches: bool = False, param_gradients=False, input_gradients=False, fused: bool = False):
     """The class that trains `model`, without creating anything (no device is asked for): `Trainer` where the fused chain takes it,
     `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise -- which is what a
     model with parameter branches gets unless `branches` is set: then a model with param_depth > 0 and at least one parameter gets
     `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it.  `param_gradients` / `input_gradients` (True or "only"): the layer-by-layer class also
-    where the chain would take the model -- the chain stops at the encoded inputs."""
+    where the chain would take the model, unless `fused` is set: then a FourierFeatures model the chain takes keeps `Trainer`, which takes both
+    gradients through `ntx_trainer_enable_gradients` (an IPE model: the library's NTX_E_UNSUPPORTED -- the cone gaussians' derivative is not
+    written, and the layer-by-layer trainer takes no IPE model)."""
     import numpy as np
-    if _chain_takes(model) and param_gradients is False and input_gradients is False:
+    wants = param_gradients is not False or input_gradients is not False
+    if _chain_takes(model) and (not wants or fused):
+        if wants and model.pos_encoding == "ipe":
+            raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "parameter / input gradients of an IPE model on the fused chain: the cone gaussians' derivative is not written")
         return Trainer
     cls = BranchTrainer if branches and model.param_depth > 0 and model.n_params > 0 else FlexTrainer
     desc, h = model.desc(), C.c_void_p()
@@ -602,9 +631,11 @@ def trainer_class_for(model, branches: bool = False, param_gradients=False, inpu
 
 def trainer_for(model, **kw):
     """`Trainer(model, **kw)`, `FlexTrainer(model, **kw)` or `BranchTrainer(model, **kw)`, whichever `trainer_class_for(model, branches=True)`
-    names; with `param_gradients` or `input_gradients` True / "only" the layer-by-layer class in any case (it is the one that takes them)."""
-    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False), input_gradients=kw.get("input_gradients", False))
-    if cls is Trainer:
+    names; with `param_gradients` or `input_gradients` True / "only" the layer-by-layer class -- or, with `fused=True` and a FourierFeatures
+    model the chain takes, the fused chain with the same two keywords."""
+    fused = bool(kw.pop("fused", False))
+    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False), input_gradients=kw.get("input_gradients", False), fused=fused)
+    if cls is Trainer and not fused:
         kw.pop("param_gradients", None)                                        # (False: the chain has no such argument)
         kw.pop("input_gradients", None)
     return cls(model, **kw)
