@@ -665,8 +665,9 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
 /* The differentiable InstanceRenderer tail (ABI v7, appended): ntx_train_forward for the instanced render -- InstanceRenderer.evaluate_model +
  * map_model_output (renderer.py:247-354, inference-only in the reference: :233) downstream of the instancer, exactly as
  * ntx_render_instanced documents them, with every activation kept, so that a network is trained, or a parameter field fitted, in the
- * scene it is rendered in.  For a handle of ntx_trainer_create_flex / ntx_trainer_create_flex_ex (parameter branches included);
- * NTX_E_UNSUPPORTED for one of ntx_trainer_create (the fused chain runs on whole rays; the layer-by-layer entries take the same model).
+ * scene it is rendered in.  For a handle of ntx_trainer_create_flex / ntx_trainer_create_flex_ex (parameter branches included), and for one
+ * of ntx_trainer_create after ntx_trainer_enable_instanced (below: the fused 8 x 256 chain on the compact rows); NTX_E_UNSUPPORTED for a
+ * handle of ntx_trainer_create that never called it (the fused chain runs on whole rays; the layer-by-layer entries take the same model).
  * The arguments are ntx_render_instanced's buffers (DEVICE): rays_d_map[N,S,3], pts[N,S,3], t_map[N,S], dists[N,S], color_last[N,3],
  * alpha_last[N], alpha_weight[N,S] (NULL = density_reweighting off), hit[N] uint8, params_map[N,S,P] (NULL when P == 0), cone_scale[N]
  * (with t_map needed only for blur_idx >= 0).  Sample (r, s) is LIVE iff hit[r] != 0 && dists[r,s] > 0.  A live sample's network inputs:
@@ -753,9 +754,28 @@ int ntx_trainer_sample_input_gradients(ntx_trainer *t, const float **d_pts, cons
  * Checked before anything is placed, and a failed call leaves both modes as they were: NTX_E_INVALID for t NULL, a mode outside 0..2, or
  * param_mode != 0 on a model without parameters; NTX_E_UNSUPPORTED for a non-zero mode on an IPE chain handle (the cone gaussians' derivative
  * is not written).  ntx_trainer_enable_param_gradients and ntx_trainer_enable_input_gradients keep refusing a chain handle.
- * Out of scope on the chain: an instanced step (refused as before), IPE models, depths / tnear_far / cone_scale, an all-reduce of these
- * gradients, second order. */
+ * An instanced step on the chain (ntx_trainer_enable_instanced) leaves the per-sample results of these modes behind
+ * ntx_trainer_sample_param_gradients / ntx_trainer_sample_input_gradients, as a layer-by-layer handle's does.
+ * Out of scope on the chain: IPE models, depths / tnear_far / cone_scale, an all-reduce of these gradients, second order. */
 int ntx_trainer_enable_gradients(ntx_trainer *t, int param_mode, int input_mode);
+/* Instanced steps on the fused 8 x 256 chain (ABI v7, appended): after this call a handle of ntx_trainer_create takes
+ * ntx_train_forward_instanced + ntx_train_backward with exactly the meaning documented there -- the live rule, the compaction in ascending
+ * (ray, sample) order, the one 8-byte read-back of n_live, nothing read at a sample that is not live, the appended sample, NTX_FLAG_MAP_EXR and
+ * NTX_FLAG_COMPOSITE_BKGD, n_live = 0 as a legal step with exactly-zero weight gradients and no network launch, one backward per forward, the
+ * same NTX_E_INVALID cases.  The chain runs on the n_live compact rows: an encoder of its own writes the live samples' pos_map / dir_map in
+ * the chain's operand layout (the values are the layer-by-layer encoder's, bit for bit), the forward chain runs without the per-ray direction
+ * hoist (every sample has a direction and appearance parameters of its own), the shared instanced composite and its adjoint stand between, and
+ * the narrow heads' dY tile is made from the adjoint's row-major result.  The weight gradients' partial sums are the chain's (a function of
+ * n_live and the device's CU count, not of the trainer's capacity); two identical steps give identical bits.  Under
+ * ntx_trainer_enable_gradients the step leaves ntx_trainer_sample_param_gradients [N][S][P] and ntx_trainer_sample_input_gradients
+ * ([N][S][3] twice) with the semantics of a layer-by-layer handle, exact zeros at samples that are not live; mode 2 contracts and reduces no
+ * weight gradient and leaves the gradient buffer alone; ntx_trainer_param_gradients / ntx_trainer_ray_gradients return NTX_E_INVALID after
+ * an instanced step.  ntx_trainer_activation after such a step: the chain's slots (0-9, 10, 11, 20-30, 40 / 41) over the COMPACT rows.
+ * The call only allocates -- the compaction's maps and scan workspace, for the trainer's capacity -- and is idempotent: plain steps after it
+ * are bit for bit what they were, and a chain handle that never calls it allocates, launches and refuses as before.
+ * NTX_OK and nothing changes for a handle of ntx_trainer_create_flex / _flex_ex (they take instanced steps already).  NTX_E_INVALID: t NULL.
+ * NTX_E_UNSUPPORTED: an IPE chain handle (IPE stays out of scope for instanced steps). */
+int ntx_trainer_enable_instanced(ntx_trainer *t);
 
 #ifdef __cplusplus
 }

@@ -50,10 +50,10 @@ class DifferentiableRender:
 
 
 class DifferentiableInstanceRender:
-    """The same op on the INSTANCED render (`FlexTrainer.forward_instanced`, `ntx_train_forward_instanced`): fine-tune a network in the scene
+    """The same op on the INSTANCED render (`Trainer.forward_instanced`, `ntx_train_forward_instanced`): fine-tune a network in the scene
     it is rendered in, or fit a parameter field to an image of the furred object.
 
-        render = DifferentiableInstanceRender(trainer, patch_scale=0.09, density_scale=400.)   # a FlexTrainer or BranchTrainer
+        render = DifferentiableInstanceRender(trainer, patch_scale=0.09, density_scale=400.)   # a FlexTrainer or BranchTrainer, or Trainer(..., instanced=True)
         color_pred, alpha_pred = render(bufs, cone_scale, params_map=field)                    # bufs: the instancer's ten-tuple
         (my_loss(color_pred, alpha_pred) + 1e-3 * field.square().sum()).backward()             # field.grad [N,S,P] from both terms
 
@@ -62,12 +62,12 @@ class DifferentiableInstanceRender:
 
     def __init__(self, trainer, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True) -> None:
         if not hasattr(trainer, "forward_instanced"):
-            raise TypeError("DifferentiableInstanceRender takes a layer-by-layer trainer (FlexTrainer, BranchTrainer): the fused chain runs on whole rays")
+            raise TypeError("DifferentiableInstanceRender takes one pass (FlexTrainer, BranchTrainer, or Trainer with instanced=True), not a coarse + fine pair")
         self.trainer = trainer
         self.opts = dict(patch_scale=float(patch_scale), density_scale=float(density_scale), density_reweighting=bool(density_reweighting))
 
     def __call__(self, bufs, cone_scale, params_map=None, **kw):
-        """`FlexTrainer.forward_instanced`'s arguments (composite_bkgd, bkgd_color, hit in `kw`); returns (color_pred [N,3], alpha_pred [N]) in
+        """`Trainer.forward_instanced`'s arguments (composite_bkgd, bkgd_color, hit in `kw`); returns (color_pred [N,3], alpha_pred [N]) in
         the autograd graph."""
         import torch
         tr = self.trainer
@@ -76,7 +76,7 @@ class DifferentiableInstanceRender:
             params_map = bufs[9]
         wants = isinstance(params_map, torch.Tensor) and params_map.requires_grad
         if wants and not getattr(tr, "param_gradients", False):
-            raise ValueError("params_map.requires_grad, but the trainer takes no parameter gradients (FlexTrainer / BranchTrainer with param_gradients=True or \"only\"); "
+            raise ValueError("params_map.requires_grad, but the trainer takes no parameter gradients (a trainer with param_gradients=True or \"only\"); "
                              "detach it, or its gradient would silently lack the render's term")
         anchor = torch.zeros((), device=torch.device("cuda", tr.device), requires_grad=True)
         ins = [a if getattr(tr, "input_gradients", False) and isinstance(a, torch.Tensor) and a.requires_grad else None for a in (bufs[1], bufs[0])]   # pts, rays_d_map

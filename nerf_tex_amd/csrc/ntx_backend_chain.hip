@@ -7,6 +7,8 @@
 //   encode_kernel   sample points and the encodings of position / direction / parameters (ntx_encode.h): the first layer's and the two
 //                   concatenations' inputs, in the row order the chain reads and in the operand order the weight gradients read
 //   dirrow_kernel   the colour layer's direction segment once per ray, where a ray's samples share it
+//   encode_samples_kernel, dhead_rows_kernel   an instanced step (ntx_trainer_enable_instanced): the same operands from the instancer's buffers
+//                   over the compact rows of the live samples, and the narrow heads' dY tile from the shared composite adjoint's row-major dgrad
 //   feat_grad_kernel  where dL/d params or dL/d rays is asked for (ntx_trainer_enable_gradients): the gradient at pos_map and dir_map, the three
 //                   products the chain back leaves out, on the f32 matrix cores; ntx_backend_flex.hip's folds take it from there
 // The handle, the composite, the loss, the partial sums' reduction and Adam are ntx_trainer.hip's.  gfx950 only.
@@ -123,6 +125,51 @@ __global__ __launch_bounds__(64) void encode_kernel(EncodeArgs args) {
         if (a.n_app > 0) fourier(fourier_width(3, a.dir_freq), a.n_app, a.param_freq, [&](int c) { return param(a.n_geo + c); });   // model.py:96-101
         if (valid && h == 0) args.dists[(size_t)ray * a.S + s] = IPE ? segment_dist(e0, e1, hit, rc.dn) : sample_dist(zray, s, a.S, z, hit, rc.dn);
     }
+}
+
+// The same operands for an instanced step (ntx_train_forward_instanced): compact row blk * 32 + n is live sample m = live[row] of the
+// instancer's buffers -- pos_map = FourierFeatures(pts[m]) | FourierFeatures(geometry parameters), dir_map = FourierFeatures(rays_d_map[m]) |
+// FourierFeatures(appearance parameters): the direction as given (renderer.py:265-272 hands it on un-normalised), the parameters params_map[m]
+// with column blur_idx times cone_scale t / patch_scale (:259-263).  Lane (n, h) as in encode_kernel, every value ntx_encode.h's: the features
+// flex_encode_samples_kernel feeds, bit for bit.  The tail of the last block is written as zeros; a lane of the tail reads nothing -- not
+// live[] beyond n_live, nor anything of the caller's, which is read at live samples alone.  The distances stay the caller's.
+struct EncodeSamplesArgs { StepSamples s; float *posO; int ptiles; float *dirO; int dtiles; };
+__global__ __launch_bounds__(64) void encode_samples_kernel(EncodeSamplesArgs args) {
+    const StepSamples &a = args.s;
+    const int lane = threadIdx.x, n = lane & 31, h = lane >> 5, blk = blockIdx.x, part = blockIdx.y;
+    const long long row = (long long)blk * 32 + n;
+    const bool valid = row < a.n_live;
+    const long long m = valid ? a.live[row] : 0, ray = m / a.S;
+    const int P = a.n_geo + a.n_app;
+    auto param = [&](int col) {
+        if (!valid) return 0.0f;
+        const float p = a.params_map[(size_t)m * P + col];
+        return col == a.blur_idx ? p * a.blur_scale(m, ray) : p;
+    };
+    float *O = part == 0 ? args.posO : args.dirO;
+    const int tiles = part == 0 ? args.ptiles : args.dtiles;
+    auto put = [&](int r, float v) { O[o_index(blk, tiles, r, n)] = valid ? v : 0.0f; };
+    auto fourier = [&](int r0, int D, int L, auto x) {
+        if (h == 0) for (int c = 0; c < D; ++c) put(r0 + c, x(c));
+        for (int f = 0; f < L; ++f)
+            for (int c = 0; c < D; ++c) put(r0 + fourier_row_of(D, f, h, c), fourier_value(x(c), f, h));
+    };
+    const float *xyz = part == 0 ? a.pts : a.rays_d_map;
+    const float x3[3] = {valid ? xyz[3 * m] : 0.0f, valid ? xyz[3 * m + 1] : 0.0f, valid ? xyz[3 * m + 2] : 0.0f};
+    const int L3 = part == 0 ? a.pos_freq : a.dir_freq, D = part == 0 ? a.n_geo : a.n_app, c0 = part == 0 ? 0 : a.n_geo;
+    fourier(0, 3, L3, [&](int c) { return c == 0 ? x3[0] : c == 1 ? x3[1] : x3[2]; });
+    if (D > 0) fourier(fourier_width(3, L3), D, a.param_freq, [&](int c) { return param(c0 + c); });
+}
+// ... and the narrow heads' dY of its way back: inst_composite_adjoint_kernel (ntx_trainer.hip, the layer-by-layer step's too) leaves the
+// row-major dgrad [n_live][4] alone; the weight gradients read rows 0 .. 3 of one O-layout tile per block (dhead_at).  Thread per row of
+// the n_live rows' blocks, the tail of the last block as zeros; rows 4 .. 31 of the tile are never written: zero as at allocation.
+__global__ __launch_bounds__(256) void dhead_rows_kernel(const float *__restrict__ dgrad, long long n_live, float *__restrict__ dhead) {
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= (n_live + 31) / 32 * 32) return;
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    const f32x4 g = m < n_live ? *reinterpret_cast<const f32x4 *>(dgrad + 4 * m) : zero;
+    dhead[o_index(m >> 5, 1, 0, (int)(m & 31))] = g.x; dhead[o_index(m >> 5, 1, 1, (int)(m & 31))] = g.y;
+    dhead[o_index(m >> 5, 1, 2, (int)(m & 31))] = g.z; dhead[o_index(m >> 5, 1, 3, (int)(m & 31))] = g.w;
 }
 
 // The colour layer's direction segment once per ray (fwd_chain_kernel's HOIST builds): row[f] = bias_C1[f] + sum_k dir_map[k] W_C1[k][f] over
@@ -247,14 +294,23 @@ struct ChainBackend : Backend {
     float *ray_pg = nullptr;                   // [cap_rays][P]: a ray's samples folded and added
     float *act_at(int i) const { return act + (size_t)i * act_stride; }
     float *gout_at(int i) const { return gout + (size_t)i * gout_stride; }
-    unsigned chain_grid(const StepRays &r) const { return (unsigned)std::min<long long>(t->cus, (r.n_blocks() + 3) / 4); }      // persistent: a workgroup of four waves per CU
-    unsigned feat_grid(const StepRays &r) const { return (unsigned)std::min<long long>(2 * (long long)t->cus, (r.n_blocks() + 3) / 4); }   // persistent: two workgroups of four waves per CU
+    bool samples_on = false;                   // ntx_trainer_enable_instanced: the handle takes instanced steps
+    static int blocks_of(long long rows) { return (int)((rows + 31) / 32); }
+    unsigned chain_grid(long long rows) const { return (unsigned)std::min<long long>(t->cus, (blocks_of(rows) + 3) / 4); }      // persistent: a workgroup of four waves per CU
+    unsigned feat_grid(long long rows) const { return (unsigned)std::min<long long>(2 * (long long)t->cus, (blocks_of(rows) + 3) / 4); }   // persistent: two workgroups of four waves per CU
     size_t plan_layers(const ntx_model_desc &d, bool ipe);
     void build_pack();
     void build_dw_jobs();
     int forward(const StepRays &r, hipStream_t st) override;
     int backward(const StepRays &r, hipStream_t st) override;
+    void launch_pack(hipStream_t st);
+    FwdArgs fwd_args(long long M) const;
+    void backward_network(long long M, hipStream_t st);
     void backward_weights(int n_blocks, hipStream_t st);
+    int takes_samples() override { return samples_on ? NTX_OK : Backend::takes_samples(); }
+    int enable_samples() override;
+    int forward_samples(const StepSamples &s, hipStream_t st) override;
+    int backward_samples(const StepSamples &s, float *sample_pg, hipStream_t st) override;
     int enable_gradients(int param_mode, int input_mode) override;
     void launch_feat_grad(hipStream_t st, unsigned grid, int tiles, const FeatGradArgs &a);
     int activation(int layer, int64_t n_samples_total, float *out_host) override;
@@ -403,16 +459,24 @@ void ChainBackend::build_dw_jobs() {
     }
 }
 
-int ChainBackend::forward(const StepRays &r, hipStream_t st) {
+void ChainBackend::launch_pack(hipStream_t st) {
     const PackArgs pa{pack_seg, n_pack, pack_total};
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((pack_total + 255) / 256)), dim3(256), 0, st, pa);
-    EncodeArgs e{}; e.r = r; e.posO = posO; e.ptiles = ptiles; e.dirO = dirO; e.dtiles = dtiles; e.dists = t->dists;
-    if (t->ipe) hipLaunchKernelGGL(encode_kernel<true>, dim3((unsigned)r.n_blocks(), 2), dim3(64), 0, st, e);
-    else hipLaunchKernelGGL(encode_kernel<false>, dim3((unsigned)r.n_blocks(), 2), dim3(64), 0, st, e);
-    FwdArgs f{}; f.stream = wfwd; f.stream_bytes = (uint32_t)(fwd_floats * sizeof(float)); f.aux = aux; f.M = r.M();
+}
+// the forward chain's arguments on M rows, less the direction hoist's
+FwdArgs ChainBackend::fwd_args(long long M) const {
+    FwdArgs f{}; f.stream = wfwd; f.stream_bytes = (uint32_t)(fwd_floats * sizeof(float)); f.aux = aux; f.M = M;
     f.ptiles = ptiles; f.dtiles = dtiles; f.pos = posO; f.dir = dirO;
     f.act = act; f.act_stride = act_stride; f.bits = bits; f.bits_stride = bits_stride;
     f.sigma = t->sigma; f.raw_rgb = t->raw_rgb;
+    return f;
+}
+int ChainBackend::forward(const StepRays &r, hipStream_t st) {
+    launch_pack(st);
+    EncodeArgs e{}; e.r = r; e.posO = posO; e.ptiles = ptiles; e.dirO = dirO; e.dtiles = dtiles; e.dists = t->dists;
+    if (t->ipe) hipLaunchKernelGGL(encode_kernel<true>, dim3((unsigned)r.n_blocks(), 2), dim3(64), 0, st, e);
+    else hipLaunchKernelGGL(encode_kernel<false>, dim3((unsigned)r.n_blocks(), 2), dim3(64), 0, st, e);
+    FwdArgs f = fwd_args(r.M());
     // the direction segment of the colour layer per ray instead of per sample -- unless blur_idx scales an APPEARANCE parameter per sample
     // (renderer.py:155-158) or a block of 32 samples can lie in two rays (S no multiple of 32).  Under the MipRenderer the parameters are
     // per-ray constants whatever blur_idx is (the blur is the cone's radius)
@@ -422,7 +486,22 @@ int ChainBackend::forward(const StepRays &r, hipStream_t st) {
         hipLaunchKernelGGL(dirrow_kernel, dim3((unsigned)r.n_rays), dim3(256), 0, st, dr);
     }
     f.dirrow = dirrow; f.n_rays = (int)r.n_rays; f.S = r.S;
-    launch_fwd_chain(fwd_variant, hoist, st, chain_grid(r), f);
+    launch_fwd_chain(fwd_variant, hoist, st, chain_grid(r.M()), f);
+    return NTX_OK;
+}
+// An instanced step: the same chain on the n_live compact rows of the step's live samples (none: nothing is launched).  Every sample has a
+// direction and appearance parameters of its own (rays_d_map, params_map), so the colour layer's direction segment is per sample: the build
+// without the hoist, the one S % 32 != 0 and an appearance blur_idx already run
+int ChainBackend::forward_samples(const StepSamples &s, hipStream_t st) {
+    if (int rc = takes_samples()) return rc;
+    const long long M = s.n_live;
+    if (M == 0) return NTX_OK;
+    launch_pack(st);
+    EncodeSamplesArgs e{}; e.s = s; e.posO = posO; e.ptiles = ptiles; e.dirO = dirO; e.dtiles = dtiles;
+    hipLaunchKernelGGL(encode_samples_kernel, dim3((unsigned)blocks_of(M), 2), dim3(64), 0, st, e);
+    FwdArgs f = fwd_args(M);
+    f.dirrow = dirrow; f.n_rays = (int)s.n_rays; f.S = s.S;                  // (not read without the hoist)
+    launch_fwd_chain(fwd_variant, false, st, chain_grid(M), f);
     return NTX_OK;
 }
 
@@ -457,25 +536,55 @@ void dump_dw_clocks(const unsigned long long *clocks, long long G, const std::ve
 }
 #endif
 
-int ChainBackend::backward(const StepRays &r, hipStream_t st) {
-    const int n_blocks = r.n_blocks();
-    DxArgs x{}; x.stream = wdx; x.stream_bytes = (uint32_t)(dx_floats * sizeof(float)); x.M = r.M(); x.dgrad = t->dgrad;
+// the way back over M rows from the handle's dgrad [M][4] and its O-layout copy dhead: the chain back, the gradient at the encoded inputs
+// where a mode asks for it, the weight gradients
+void ChainBackend::backward_network(long long M, hipStream_t st) {
+    DxArgs x{}; x.stream = wdx; x.stream_bytes = (uint32_t)(dx_floats * sizeof(float)); x.M = M; x.dgrad = t->dgrad;
     x.out = gout; x.out_stride = gout_stride; x.bits = bits; x.bits_stride = bits_stride;
-    launch_dx_chain(st, chain_grid(r), x);
+    launch_dx_chain(st, chain_grid(M), x);
     if (t->pg_mode != 0 || t->ig_mode != 0) {                                // the gradient at pos_map and at dir_map, all Kp / Kd columns whichever mode asked
         FeatGradArgs p{}; p.dY[0] = gout_at(10); p.W[0] = t->w + trunk[0].w; p.dY[1] = gout_at(5); p.W[1] = t->w + trunk[5].w; p.n_terms = 2;
-        p.K = t->Kp; p.ld = ld_pos; p.M = r.M(); p.G = G_pos;
-        launch_feat_grad(st, feat_grid(r), ptiles, p);
-        FeatGradArgs d{}; d.dY[0] = gout_at(1); d.W[0] = t->w + c1.w; d.n_terms = 1; d.K = t->Kd; d.ld = ld_dir; d.M = r.M(); d.G = G_dir;
-        launch_feat_grad(st, feat_grid(r), dtiles, d);
+        p.K = t->Kp; p.ld = ld_pos; p.M = M; p.G = G_pos;
+        launch_feat_grad(st, feat_grid(M), ptiles, p);
+        FeatGradArgs d{}; d.dY[0] = gout_at(1); d.W[0] = t->w + c1.w; d.n_terms = 1; d.K = t->Kd; d.ld = ld_dir; d.M = M; d.G = G_dir;
+        launch_feat_grad(st, feat_grid(M), dtiles, d);
     }
-    if (t->takes_weight_gradients()) backward_weights(n_blocks, st);         // either mode 2: no weight gradient is taken or reduced
+    if (t->takes_weight_gradients()) backward_weights(blocks_of(M), st);     // either mode 2: no weight gradient is taken or reduced
+}
+int ChainBackend::backward(const StepRays &r, hipStream_t st) {
+    backward_network(r.M(), st);
     // the folds of the layer-by-layer backend: the parameter features' and the FF(xyz) / FF(dir) rows' gradient through the encoder
     if (t->pg_mode != 0) {
         const ntx_model_desc &m = t->desc;
         launch_param_fold(st, r, G_pos + 3 * (1 + 2 * m.pos_freq), G_dir + 3 * (1 + 2 * m.dir_freq), ld_pos, ld_dir, ray_pg, t->P, t->param_grad);
     }
     if (t->ig_mode != 0) launch_ray_fold(st, r, G_pos, G_dir, ld_pos, ld_dir, t->dgrad, t->sigma, t->step_noise, t->d_rays_o, t->d_rays_d);
+    return NTX_OK;
+}
+// An instanced step's way back over its n_live rows, from the shared composite adjoint's dgrad.  Without a live sample nothing is contracted:
+// every weight gradient is exactly 0 (mode 2 leaves the buffer alone, as ever), and the per-sample gradients are zeros.  The per-sample folds
+// are the layer-by-layer backend's, on feat_grad_kernel's rows at row_of[m]
+int ChainBackend::backward_samples(const StepSamples &s, float *sample_pg, hipStream_t st) {
+    if (int rc = takes_samples()) return rc;
+    const long long M = s.n_live;
+    if (M > 0) {
+        hipLaunchKernelGGL(dhead_rows_kernel, dim3((unsigned)((blocks_of(M) * 32 + 255) / 256)), dim3(256), 0, st, t->dgrad, M, t->dhead);
+        backward_network(M, st);
+    } else if (t->takes_weight_gradients()) TRAIN_TRY(hipMemsetAsync(t->grad, 0, t->n_weights * sizeof(float), st));
+    const ntx_model_desc &m = t->desc;
+    if (t->pg_mode != 0) launch_param_samples(st, s, G_pos + 3 * (1 + 2 * m.pos_freq), G_dir + 3 * (1 + 2 * m.dir_freq), ld_pos, ld_dir, t->P, sample_pg);
+    if (t->ig_mode != 0) launch_input_samples(st, s, G_pos, G_dir, ld_pos, ld_dir, t->d_pts, t->d_dirs);
+    return NTX_OK;
+}
+// ntx_trainer_enable_instanced: what an instanced step needs beyond the plain one's buffers is the compaction's maps and scan workspace, placed
+// here for the trainer's capacity (the encoded inputs, the activations and the heads' tile are the plain step's, whose capacity covers any
+// n_live).  A handle that never asks has none of it and refuses the step as before
+int ChainBackend::enable_samples() {
+    if (t->ipe) return ntx_set_error(NTX_E_UNSUPPORTED, "an instanced step of an IPE model: the instanced render has no cone segments (out of scope, as on the layer-by-layer trainer)");
+    if (samples_on) return NTX_OK;
+    TRAIN_TRY(hipSetDevice(t->device));
+    if (int rc = t->place_sample_maps()) return rc;
+    samples_on = true;
     return NTX_OK;
 }
 void ChainBackend::backward_weights(int n_blocks, hipStream_t st) {
@@ -535,7 +644,7 @@ int ChainBackend::activation(int layer, int64_t n_samples_total, float *out_host
     else if (layer == 29) src = gout_at(2);
     else if (layer == 11) src = t->raw_rgb;
     else if (layer == 30) src = t->dgrad;
-    else if ((layer == 40 || layer == 41) && G_pos && ((t->pg_mode != 0 && t->pg_rows > 0) || (t->ig_mode != 0 && t->ig_rays > 0))) src = layer == 40 ? G_pos : G_dir;
+    else if ((layer == 40 || layer == 41) && G_pos && ((t->pg_mode != 0 && (t->pg_rows > 0 || t->spg_rays > 0)) || (t->ig_mode != 0 && (t->ig_rays > 0 || t->ig_smp_rays > 0)))) src = layer == 40 ? G_pos : G_dir;
     else return ntx_set_error(NTX_E_INVALID, "layer %d (0-7 trunk, 8 / 9 the colour layers, 10 the density, 11 the raw colour; 20-29 the kept gradients, 30 the composite's adjoint; "
                               "40 / 41 the gradient at pos_map / dir_map of a step under ntx_trainer_enable_gradients)", layer);
     TRAIN_TRY(hipSetDevice(t->device));

@@ -688,14 +688,8 @@ int FlexBackend::backward(const StepRays &r, hipStream_t st) {
 int FlexBackend::backward_samples(const StepSamples &s, float *sample_pg, hipStream_t st) {
     if (s.n_live > 0) network_backward(s.n_live, st);
     else if (t->takes_weight_gradients()) TRAIN_TRY(hipMemsetAsync(t->grad, 0, t->n_weights * sizeof(float), st));
-    if (t->pg_mode != 0) {
-        FlexSampleFoldArgs f{}; f.s = s; f.pg_geo = PG[0]; f.pg_app = PG[1]; f.ld_geo = ldpg[0]; f.ld_app = ldpg[1]; f.out = sample_pg;
-        hipLaunchKernelGGL(flex_param_samples_kernel, dim3((unsigned)((s.M() * t->P + 255) / 256)), dim3(256), 0, st, f);
-    }
-    if (t->ig_mode != 0) {                                                   // (no live sample: every row_of is -1, both results are zeros)
-        FlexSampleInputArgs f{}; f.s = s; f.ig_pos = IG[0]; f.ig_dir = IG[1]; f.ld_pos = ldig[0]; f.ld_dir = ldig[1]; f.d_pts = t->d_pts; f.d_dirs = t->d_dirs;
-        hipLaunchKernelGGL(flex_input_samples_kernel, dim3((unsigned)((s.M() * 6 + 255) / 256)), dim3(256), 0, st, f);
-    }
+    if (t->pg_mode != 0) launch_param_samples(st, s, PG[0], PG[1], ldpg[0], ldpg[1], t->P, sample_pg);
+    if (t->ig_mode != 0) launch_input_samples(st, s, IG[0], IG[1], ldig[0], ldig[1], t->d_pts, t->d_dirs);      // (no live sample: every row_of is -1, both results are zeros)
     return NTX_OK;
 }
 void FlexBackend::network_backward(long long M, hipStream_t st) {
@@ -823,6 +817,14 @@ void launch_ray_fold(hipStream_t st, const StepRays &r, const float *ig_pos, con
     FlexRayFoldArgs f{}; f.r = r; f.ig_pos = ig_pos; f.ig_dir = ig_dir; f.ld_pos = ld_pos; f.ld_dir = ld_dir; f.dgrad = dgrad; f.sigma = sigma;
     f.noise = noise; f.d_rays_o = d_rays_o; f.d_rays_d = d_rays_d;
     hipLaunchKernelGGL(flex_ray_fold_kernel, dim3((unsigned)((r.n_rays + 3) / 4)), dim3(256), 0, st, f);
+}
+void launch_param_samples(hipStream_t st, const StepSamples &s, const float *pg_geo, const float *pg_app, int ld_geo, int ld_app, int P, float *out) {
+    FlexSampleFoldArgs f{}; f.s = s; f.pg_geo = pg_geo; f.pg_app = pg_app; f.ld_geo = ld_geo; f.ld_app = ld_app; f.out = out;
+    hipLaunchKernelGGL(flex_param_samples_kernel, dim3((unsigned)((s.M() * P + 255) / 256)), dim3(256), 0, st, f);
+}
+void launch_input_samples(hipStream_t st, const StepSamples &s, const float *ig_pos, const float *ig_dir, int ld_pos, int ld_dir, float *d_pts, float *d_dirs) {
+    FlexSampleInputArgs f{}; f.s = s; f.ig_pos = ig_pos; f.ig_dir = ig_dir; f.ld_pos = ld_pos; f.ld_dir = ld_dir; f.d_pts = d_pts; f.d_dirs = d_dirs;
+    hipLaunchKernelGGL(flex_input_samples_kernel, dim3((unsigned)((s.M() * 6 + 255) / 256)), dim3(256), 0, st, f);
 }
 
 int flex_backend_create(ntx_trainer *t) {

@@ -73,6 +73,9 @@ struct Backend {
         return ntx_set_error(NTX_E_UNSUPPORTED, "an instanced step: the fused chain (ntx_trainer_create) runs on whole rays; the layer-by-layer trainer takes the "
                              "same model on the in-patch samples (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
     }
+    // ntx_trainer_enable_instanced: a backend that takes samples only once it is asked to (the chain) places what it needs, once; the
+    // layer-by-layer backend takes them as it is
+    virtual int enable_samples() { return takes_samples(); }
     virtual int forward_samples(const StepSamples &, hipStream_t) { return takes_samples(); }
     virtual int backward_samples(const StepSamples &, float *, hipStream_t) { return takes_samples(); }
     // ntx_trainer_enable_param_gradients, mode 1 / 2 on a model with parameters: places what dL/d params needs (once); the handle keeps the mode
@@ -125,6 +128,12 @@ struct ntx_trainer {
     float *d_rays_o = nullptr, *d_rays_d = nullptr, *d_pts = nullptr, *d_dirs = nullptr;
     long long ig_rays = 0, ig_smp_rays = 0; int ig_S = 0;
     const float *step_noise = nullptr;         // the density noise of the step whose way back runs (NULL without NTX_FLAG_RAW_NOISE): the ray fold's |d| term reads it
+    // the compaction's maps and scan workspace, for the capacity: at the first instanced step, or at ntx_trainer_enable_instanced
+    int place_sample_maps() {
+        if (live) return mem.rc;                           // (a failed allocation sticks in mem.rc)
+        mem.alloc(&live, (size_t)cap); mem.alloc(&row_of, (size_t)cap); mem.alloc(&ray_live, (size_t)cap_rays); mem.alloc(&n_live_dev, 1);
+        return mem.rc;
+    }
     bool takes_weight_gradients() const { return pg_mode != 2 && ig_mode != 2; }   // the weight gradient is taken unless EITHER mode is 2
     long long adam_iterations = 0;
     // ntx_train_forward's step until its ntx_train_backward: the caller's rays (alive and unchanged until then), what the composite was run with;
@@ -167,6 +176,10 @@ void launch_reduce(hipStream_t st, const ReduceBatch &b);
 void launch_param_fold(hipStream_t st, const StepRays &r, const float *pg_geo, const float *pg_app, int ld_geo, int ld_app, float *ray_pg, int P, float *param_grad);
 void launch_ray_fold(hipStream_t st, const StepRays &r, const float *ig_pos, const float *ig_dir, int ld_pos, int ld_dir, const float *dgrad, const float *sigma,
                      const float *noise, float *d_rays_o, float *d_rays_d);
+// ... and the two per-sample folds of an instanced step (flex_param_samples_kernel -> out [N][S][P]; flex_input_samples_kernel -> d_pts,
+// d_dirs [N][S][3]): the same rows, read at row_of[m]
+void launch_param_samples(hipStream_t st, const StepSamples &s, const float *pg_geo, const float *pg_app, int ld_geo, int ld_app, int P, float *out);
+void launch_input_samples(hipStream_t st, const StepSamples &s, const float *ig_pos, const float *ig_dir, int ld_pos, int ld_dir, float *d_pts, float *d_dirs);
 inline int pad4(int n) { return (n + 3) & ~3; }      // a row of n floats padded to 16 bytes
 __device__ __forceinline__ float wave_sumf(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
 }   // namespace ntx_train

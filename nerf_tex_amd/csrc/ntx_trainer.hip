@@ -717,11 +717,7 @@ int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const f
         return ntx_set_error(NTX_E_INVALID, "NTX_FLAG_PERTURB / NTX_FLAG_RAW_NOISE: the instancer places the samples, and the density noise of an instanced step is not built");
     hipStream_t st = (hipStream_t)stream;
     TRAIN_TRY(hipSetDevice(t->device));
-    if (!t->live) {                                                                             // the first instanced step places its maps, for the capacity
-        DeviceMemory &mem = t->mem;
-        mem.alloc(&t->live, (size_t)t->cap); mem.alloc(&t->row_of, (size_t)t->cap); mem.alloc(&t->ray_live, (size_t)t->cap_rays); mem.alloc(&t->n_live_dev, 1);
-        if (mem.rc != NTX_OK) return mem.rc;
-    }
+    if (int rc = t->place_sample_maps()) return rc;                                             // the first instanced step places its maps, for the capacity
     const unsigned ray_grid = (unsigned)((n_rays + 3) / 4);
     hipLaunchKernelGGL(live_count_kernel, dim3(ray_grid), dim3(256), 0, st, dists, hit, (long long)n_rays, n_samples, t->ray_live);
     hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, t->ray_live, (long long)n_rays, t->n_live_dev);
@@ -743,6 +739,11 @@ int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const f
     for (int k = 0; k < 3; ++k) t->pending.bkgd[k] = c.bkgd[k];
     t->pending.open = true;
     return NTX_OK;
+}
+
+int ntx_trainer_enable_instanced(ntx_trainer *t) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    return t->backend->enable_samples();                                                        // the chain places its maps once; a layer-by-layer handle takes samples as it is
 }
 
 int ntx_trainer_sample_param_gradients(ntx_trainer *t, const float **grad_dev, int64_t *n_rays, int *n_samples, int *n_params) {

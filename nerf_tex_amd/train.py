@@ -22,8 +22,9 @@ fits parameters to target images with it.  The fused chain takes the same two ke
 `ntx_trainer_enable_gradients`), and `trainer_for(model, ..., fused=True)` keeps such a model on it when a gradient is asked for.
 The losses of `nerf_tex_amd.loss` are evaluated inside the step; any other loss is a callable on
 torch tensors, and the step runs as `forward(...)`, the loss and its two cotangents in torch, `backward(d_color, d_alpha)`
-(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op).  The layer-by-layer trainers also take the step through
-the INSTANCED render (`forward_instanced(bufs, ...)` on an instancer's buffers, then the same `backward`; `DifferentiableInstanceRender`)."""
+(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op).  Every trainer also takes the step through
+the INSTANCED render (`forward_instanced(bufs, ...)` on an instancer's buffers, then the same `backward`; `DifferentiableInstanceRender`):
+the layer-by-layer ones as they are, the fused chain for a FourierFeatures model once asked (`instanced=True`, `enable_instanced()`)."""
 
 from __future__ import annotations
 
@@ -36,14 +37,15 @@ from . import _lib
 class Trainer:
     def __init__(self, model, max_rays: int, n_samples: int, lrate: float = 5e-4, lrate_decay: float = 0, perturb: bool = True, blur_idx: Optional[int] = None,
                  map_exr: bool = False, raw_noise_std: float = 0.0, beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, device: int = 0,
-                 param_gradients=False, input_gradients=False) -> None:
+                 param_gradients=False, input_gradients=False, instanced: bool = False) -> None:
         """`model`: a nerf_tex_amd.model.ParamNerf container (its blob gives the initial weights); `lrate`, `lrate_decay` as train.py:49-50
         (ExponentialDecay(lrate, decay_steps=lrate_decay * 1e3, decay_rate=0.1) when lrate_decay > 0); `perturb`, `blur_idx`, `map_exr`: the
         renderer's (renderer.py:34); `raw_noise_std`: the density regulariser of map_model_output (renderer.py:190-192; config_grass_filtered_train.py:99
         trains with 0.1), drawn per (seed, ray, sample) like the jitter.  An IPE model (pos_encoding 'ipe', n_pos 6) trains as the MipRenderer
         renders it (renderer.py:365-444): `n_samples` cone segments between n_samples + 1 depths, the parameter rows hold the blur parameter at
         `blur_idx` (required) -- its product with cone_scale is the cone's radius, and the model sees the other parameters.
-        `param_gradients` / `input_gradients`: False, True or "only" (`set_gradients`), for a FourierFeatures model."""
+        `param_gradients` / `input_gradients`: False, True or "only" (`set_gradients`), for a FourierFeatures model.  `instanced`: the trainer
+        also takes steps through the instanced render (`enable_instanced`, `forward_instanced`), for a FourierFeatures model."""
         import numpy as np
         self.mip = getattr(model, "pos_encoding", "fourier") == "ipe"
         if self.mip and blur_idx is None:
@@ -76,6 +78,8 @@ class Trainer:
         self.param_gradients = self.input_gradients = False
         if param_gradients is not False or input_gradients is not False:
             self.set_gradients(param_gradients, input_gradients)
+        if instanced:
+            self.enable_instanced()
 
     _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create(*a))           # the entry that makes the native trainer
     _widen = staticmethod(lambda model: _widened(model))                           # a narrower network inside the 256-wide one
@@ -344,6 +348,14 @@ class Trainer:
             _lib.check(_lib.lib.ntx_trainer_enable_gradients(self._h, native[0], native[1]))
         self.param_gradients, self.input_gradients = ("only" if m == 2 else bool(m) for m in native)
 
+    def enable_instanced(self) -> None:
+        """From here on the trainer takes `forward_instanced` (`ntx_trainer_enable_instanced`): the fused chain places the compaction's maps
+        for its capacity, once; plain steps stay bit for bit what they were.  A layer-by-layer trainer takes instanced steps as it is and
+        nothing changes; an IPE model: NTX_E_UNSUPPORTED."""
+        import torch
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.ntx_trainer_enable_instanced(self._h))
+
     def _device_copies(self, ptrs, shape):
         """Copies of the trainer's device results `ptrs` as torch tensors of `shape`, in the current stream's order."""
         import torch
@@ -370,6 +382,69 @@ class Trainer:
         _lib.check(_lib.lib.ntx_trainer_param_gradients(self._h, C.byref(ptr), C.byref(rows), C.byref(n)))
         dev = torch.device("cuda", self.device)
         out = torch.empty((int(rows.value), int(n.value)), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def sample_input_gradients(self):
+        """(dL/d pts, dL/d rays_d_map) of the last INSTANCED step: torch tensors [N, S, 3] on the trainer's device (exact zeros at samples
+        outside every patch), copies in the current stream's order."""
+        p, d, n, s = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int()
+        _lib.check(_lib.lib.ntx_trainer_sample_input_gradients(self._h, C.byref(p), C.byref(d), C.byref(n), C.byref(s)))
+        return self._device_copies((p, d), (int(n.value), int(s.value), 3))
+
+    def forward_instanced(self, bufs, cone_scale, *, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True, composite_bkgd: bool = False,
+                          bkgd_color=(1., 1., 1.), hit=None):
+        """The first half of a step on the INSTANCED render (`ntx_train_forward_instanced`): InstanceRenderer's tail (renderer.py:247-354) with
+        every activation kept, the network on the in-patch samples alone.  `bufs`: the ten-tuple of an instancer's `get_model_input` --
+        rays_d_map [N,S,3], pts [N,S,3], t [N,S], dists [N,S], color_last [N,1,3], alpha_last [N,1], alpha_weight [N,S], instance_id (unused),
+        idxs (indices of the hit rays [k,1] or a bool mask [N]), params_map [N,S,P] -- as numpy arrays or tensors; `hit` [N] (the native
+        instancer's `last_hit`) takes the place of idxs.  `cone_scale` [N] (read with blur_idx only).  Returns (color_pred [N,3], alpha_pred
+        [N]) as GPU tensors and leaves the step pending until `backward(d_color, d_alpha)`, exactly as `forward` does; `self.last_live` is
+        the number of in-patch samples the network ran on (reading it back is the step's one synchronisation).  Float32, contiguous device
+        tensors are read in place and must not be written before the backward."""
+        import numpy as np
+        import torch
+        dev, to, ptr = self._device_tools()
+        self._pending = None
+        rays_d_map, pts, tt, dists, color_last, alpha_last, alpha_weight, _, idxs, params_map = bufs
+        dists = to(dists)
+        n, S = int(dists.shape[0]), int(dists.shape[1])
+        if hit is None:
+            idxs = idxs.detach().cpu().numpy() if isinstance(idxs, torch.Tensor) else np.asarray(idxs)
+            mask = np.zeros(n, np.uint8)
+            mask[idxs.reshape(-1) if idxs.dtype == np.bool_ else idxs.reshape(-1).astype(np.int64)] = 1
+            hit = mask
+        hit = (hit if isinstance(hit, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(hit))).to(device=dev).ne(0).to(torch.uint8).contiguous()
+        P = int(getattr(self.model, "n_params", 0))
+        keep = dict(rd=to(rays_d_map), pts=to(pts), t=to(tt), dists=dists, cl=to(color_last), al=to(alpha_last), aw=to(alpha_weight) if density_reweighting else None, hit=hit,
+                    pm=to(params_map) if P > 0 else None, cone=to(cone_scale))
+        sizes = dict(rd=3 * n * S, pts=3 * n * S, t=n * S, cl=3 * n, al=n, aw=n * S, hit=n, pm=n * S * P, cone=n)
+        for k, want in sizes.items():
+            if keep[k] is not None and keep[k].numel() != want:
+                raise ValueError(f"forward_instanced: buffer '{k}' holds {keep[k].numel()} elements, {n} rays x {S} samples need {want}")
+        flags = (_lib.FLAG_MAP_EXR if self.map_exr else 0) | (_lib.FLAG_COMPOSITE_BKGD if composite_bkgd else 0)
+        color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev)
+        live = C.c_int64(0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.ntx_train_forward_instanced(
+                self._h, ptr(keep["rd"]), ptr(keep["pts"]), ptr(keep["t"]), ptr(dists), ptr(keep["cl"]), ptr(keep["al"]), ptr(keep["aw"]), ptr(hit), ptr(keep["pm"]),
+                ptr(keep["cone"]), n, S, -1 if self.blur_idx is None else int(self.blur_idx), float(patch_scale), float(density_scale), flags, _lib.f3(bkgd_color),
+                ptr(color), ptr(alpha), C.byref(live), torch.cuda.current_stream(dev).cuda_stream))
+        self.last_live = int(live.value)
+        self._last_rays = n
+        self._forwards += 1
+        self._pending = (self._forwards, n, keep)
+        return color, alpha
+
+    def sample_parameter_gradients(self):
+        """dL/d params_map of the last INSTANCED step: a torch tensor [N, S, P] on the trainer's device (geometry columns first, exact zeros at
+        samples outside every patch), a copy in the current stream's order."""
+        import torch
+        ptr, n, s, p = C.c_void_p(), C.c_int64(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib.ntx_trainer_sample_param_gradients(self._h, C.byref(ptr), C.byref(n), C.byref(s), C.byref(p)))
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((int(n.value), int(s.value), int(p.value)), device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
         return out
@@ -442,9 +517,9 @@ class FlexTrainer(Trainer):
     _create = staticmethod(lambda *a: _lib.lib.ntx_trainer_create_flex(*a))
     _widen = staticmethod(lambda model: None)                                      # every width trains as it is
 
-    def __init__(self, model, *args, param_gradients=False, input_gradients=False, **kw) -> None:
-        """`Trainer`'s arguments, and `param_gradients`: False, True -- every `gradients_step` also leaves dL/d parameters
-        (`parameter_gradients()`), the weight gradients bit for bit as without it -- or "only": the same parameter gradients and no weight
+    def __init__(self, model, *args, param_gradients=False, input_gradients=False, instanced: bool = False, **kw) -> None:
+        """`Trainer`'s arguments (`instanced` is accepted and changes nothing: this trainer takes instanced steps as it is), and
+        `param_gradients`: False, True -- every `gradients_step` also leaves dL/d parameters (`parameter_gradients()`), the weight gradients bit for bit as without it -- or "only": the same parameter gradients and no weight
         gradient at all (`gradients()` keeps what it held; `apply_gradients` raises NTX_E_INVALID).  For a model with parameters
         (`ntx_trainer_enable_param_gradients`).  `input_gradients`: the same three values for dL/d rays_o, rays_d (`ray_gradients()`) and,
         of an instanced step, dL/d pts, rays_d_map (`sample_input_gradients()`), for any model (`ntx_trainer_enable_input_gradients`); no
@@ -480,69 +555,6 @@ class FlexTrainer(Trainer):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib.ntx_trainer_enable_input_gradients(self._h, native))
         self.input_gradients = "only" if native == 2 else bool(native)
-
-    def sample_input_gradients(self):
-        """(dL/d pts, dL/d rays_d_map) of the last INSTANCED step: torch tensors [N, S, 3] on the trainer's device (exact zeros at samples
-        outside every patch), copies in the current stream's order."""
-        p, d, n, s = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int()
-        _lib.check(_lib.lib.ntx_trainer_sample_input_gradients(self._h, C.byref(p), C.byref(d), C.byref(n), C.byref(s)))
-        return self._device_copies((p, d), (int(n.value), int(s.value), 3))
-
-    def forward_instanced(self, bufs, cone_scale, *, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True, composite_bkgd: bool = False,
-                          bkgd_color=(1., 1., 1.), hit=None):
-        """The first half of a step on the INSTANCED render (`ntx_train_forward_instanced`): InstanceRenderer's tail (renderer.py:247-354) with
-        every activation kept, the network on the in-patch samples alone.  `bufs`: the ten-tuple of an instancer's `get_model_input` --
-        rays_d_map [N,S,3], pts [N,S,3], t [N,S], dists [N,S], color_last [N,1,3], alpha_last [N,1], alpha_weight [N,S], instance_id (unused),
-        idxs (indices of the hit rays [k,1] or a bool mask [N]), params_map [N,S,P] -- as numpy arrays or tensors; `hit` [N] (the native
-        instancer's `last_hit`) takes the place of idxs.  `cone_scale` [N] (read with blur_idx only).  Returns (color_pred [N,3], alpha_pred
-        [N]) as GPU tensors and leaves the step pending until `backward(d_color, d_alpha)`, exactly as `forward` does; `self.last_live` is
-        the number of in-patch samples the network ran on (reading it back is the step's one synchronisation).  Float32, contiguous device
-        tensors are read in place and must not be written before the backward."""
-        import numpy as np
-        import torch
-        dev, to, ptr = self._device_tools()
-        self._pending = None
-        rays_d_map, pts, tt, dists, color_last, alpha_last, alpha_weight, _, idxs, params_map = bufs
-        dists = to(dists)
-        n, S = int(dists.shape[0]), int(dists.shape[1])
-        if hit is None:
-            idxs = idxs.detach().cpu().numpy() if isinstance(idxs, torch.Tensor) else np.asarray(idxs)
-            mask = np.zeros(n, np.uint8)
-            mask[idxs.reshape(-1) if idxs.dtype == np.bool_ else idxs.reshape(-1).astype(np.int64)] = 1
-            hit = mask
-        hit = (hit if isinstance(hit, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(hit))).to(device=dev).ne(0).to(torch.uint8).contiguous()
-        P = int(getattr(self.model, "n_params", 0))
-        keep = dict(rd=to(rays_d_map), pts=to(pts), t=to(tt), dists=dists, cl=to(color_last), al=to(alpha_last), aw=to(alpha_weight) if density_reweighting else None, hit=hit,
-                    pm=to(params_map) if P > 0 else None, cone=to(cone_scale))
-        sizes = dict(rd=3 * n * S, pts=3 * n * S, t=n * S, cl=3 * n, al=n, aw=n * S, hit=n, pm=n * S * P, cone=n)
-        for k, want in sizes.items():
-            if keep[k] is not None and keep[k].numel() != want:
-                raise ValueError(f"forward_instanced: buffer '{k}' holds {keep[k].numel()} elements, {n} rays x {S} samples need {want}")
-        flags = (_lib.FLAG_MAP_EXR if self.map_exr else 0) | (_lib.FLAG_COMPOSITE_BKGD if composite_bkgd else 0)
-        color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev)
-        live = C.c_int64(0)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib.ntx_train_forward_instanced(
-                self._h, ptr(keep["rd"]), ptr(keep["pts"]), ptr(keep["t"]), ptr(dists), ptr(keep["cl"]), ptr(keep["al"]), ptr(keep["aw"]), ptr(hit), ptr(keep["pm"]),
-                ptr(keep["cone"]), n, S, -1 if self.blur_idx is None else int(self.blur_idx), float(patch_scale), float(density_scale), flags, _lib.f3(bkgd_color),
-                ptr(color), ptr(alpha), C.byref(live), torch.cuda.current_stream(dev).cuda_stream))
-        self.last_live = int(live.value)
-        self._last_rays = n
-        self._forwards += 1
-        self._pending = (self._forwards, n, keep)
-        return color, alpha
-
-    def sample_parameter_gradients(self):
-        """dL/d params_map of the last INSTANCED step: a torch tensor [N, S, P] on the trainer's device (geometry columns first, exact zeros at
-        samples outside every patch), a copy in the current stream's order."""
-        import torch
-        ptr, n, s, p = C.c_void_p(), C.c_int64(), C.c_int(), C.c_int()
-        _lib.check(_lib.lib.ntx_trainer_sample_param_gradients(self._h, C.byref(ptr), C.byref(n), C.byref(s), C.byref(p)))
-        dev = torch.device("cuda", self.device)
-        out = torch.empty((int(n.value), int(s.value), int(p.value)), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.copy_device_async(out.data_ptr(), ptr.value, out.numel() * 4, torch.cuda.current_stream(dev).cuda_stream)
-        return out
 
     def relu_widths(self):
         """Widths of the ReLU layers in the order of `activation`'s indices (and of the oracle's masks): trunk, colour layers, colour half."""
@@ -632,7 +644,8 @@ def trainer_class_for(model, branches: bool = False, param_gradients=False, inpu
 def trainer_for(model, **kw):
     """`Trainer(model, **kw)`, `FlexTrainer(model, **kw)` or `BranchTrainer(model, **kw)`, whichever `trainer_class_for(model, branches=True)`
     names; with `param_gradients` or `input_gradients` True / "only" the layer-by-layer class -- or, with `fused=True` and a FourierFeatures
-    model the chain takes, the fused chain with the same two keywords."""
+    model the chain takes, the fused chain with the same two keywords.  `instanced=True` goes on to the class: the chain then takes instanced
+    steps too (the layer-by-layer classes always do)."""
     fused = bool(kw.pop("fused", False))
     cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False), input_gradients=kw.get("input_gradients", False), fused=fused)
     if cls is Trainer and not fused:
