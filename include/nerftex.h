@@ -17,7 +17,40 @@
  *     the instance matrices and the instancer's hit lists); no other entry point allocates or frees device memory;
  *   - every entry point is asynchronous on `stream` (a `hipStream_t` passed as `void*`; NULL = the
  *     null stream) and returns an `ntx_status` (0 = ok, negative = error).  The message of the
- *     last error on the calling thread is returned by `ntx_last_error()`;
+ *     last error on the calling thread is returned by `ntx_last_error()`.  An entry that takes a `stream` touches no stream but
+ *     that one and waits for nothing -- its launches, memsets and copies are all queued on `stream` -- so callers may use
+ *     non-blocking streams and order handles against each other with events (tests/test_gpu_streams.py).  The entries that wait, and
+ *     for what ("device": every stream of the device; "stream": the `stream` they were given, once; "setup": creation and setup
+ *     entries -- they allocate, upload with blocking copies behind the null stream's work, and a free waits for the device; call
+ *     them before the work they configure, or after it has completed).  synchronisation table:
+ *         ntx_reserve                            device
+ *         ntx_set_weights                        device
+ *         ntx_trainer_get                        device
+ *         ntx_trainer_set                        device
+ *         ntx_trainer_set_weights                device
+ *         ntx_trainer_activation                 device
+ *         ntx_train_forward_instanced            stream
+ *         ntx_create                             setup
+ *         ntx_destroy                            setup
+ *         ntx_comm_create                        setup
+ *         ntx_comm_destroy                       setup
+ *         ntx_trainer_create                     setup
+ *         ntx_trainer_create_flex                setup
+ *         ntx_trainer_create_flex_ex             setup
+ *         ntx_trainer_destroy                    setup
+ *         ntx_trainer_enable_param_gradients     setup
+ *         ntx_trainer_enable_input_gradients     setup
+ *         ntx_trainer_enable_gradients           setup
+ *         ntx_trainer_enable_instanced           setup
+ *         ntx_instancer_create                   setup
+ *         ntx_instancer_destroy                  setup
+ *         ntx_instancer_reserve                  setup
+ *         ntx_instancer_set_mesh                 setup
+ *         ntx_instancer_set_meshes               setup
+ *         ntx_instancer_set_parameter_textures   setup
+ *         ntx_instancer_set_mesh_textures        setup
+ *     end of table.  The first ntx_set_weights_device of a context also uploads its gather tables with blocking copies (behind the
+ *     null stream's work) before it queues its kernel on `stream`; every later call only queues;
  *   - a context belongs to one device; calls on one context are not re-entrant.  Multi-GPU =
  *     one context (and one process) per device.
  */
@@ -162,7 +195,9 @@ size_t ntx_weight_count(const ntx_model_desc *desc);
  * Packs the HOST blob into the MFMA operand layout and uploads it to `device`. */
 int ntx_create(const ntx_model_desc *desc, const float *weights_host, size_t n_floats, int device,
                ntx_ctx **out);
-/* Re-pack and re-upload new weights into an existing context (synchronous). */
+/* Re-pack and re-upload new weights into an existing context.  Synchronous: it waits for all work on the context's device, on every
+ * stream -- a launch in flight reads the old weights to its end -- and it has returned only once the upload is complete: every launch
+ * made after it, on any stream, reads the new ones. */
 int ntx_set_weights(ntx_ctx *ctx, const float *weights_host, size_t n_floats);
 int ntx_destroy(ntx_ctx *ctx);
 

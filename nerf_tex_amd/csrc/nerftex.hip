@@ -262,6 +262,7 @@ int ntx_set_weights(ntx_ctx *ctx, const float *weights_host, size_t n_floats) {
     const int rc = ntx_pack_weights(&ctx->descx.base, weights_host, n_floats, packed.data(), packed.size());
     if (rc != NTX_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());   // a launch on any stream may still be reading the images (a blocking copy waits for the null stream alone)
     HIP_TRY(hipMemcpy(ctx->packed, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
     if (ctx->packed16) {
         std::vector<uint16_t> p16(ctx->packed16_bytes / 2);
