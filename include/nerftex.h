@@ -811,6 +811,30 @@ int ntx_trainer_enable_gradients(ntx_trainer *t, int param_mode, int input_mode)
  * NTX_OK and nothing changes for a handle of ntx_trainer_create_flex / _flex_ex (they take instanced steps already).  NTX_E_INVALID: t NULL.
  * NTX_E_UNSUPPORTED: an IPE chain handle (IPE stays out of scope for instanced steps). */
 int ntx_trainer_enable_instanced(ntx_trainer *t);
+/* Losses on the compositing weights (ABI v7, appended): a loss that looks ALONG the ray -- an expected depth sum_s w_s z_s against a depth
+ * target, an entropy or distortion regulariser on the weights, a proposal loss for a sampler -- is a function of the weights
+ * w_s = a_s T_s, not of color_pred and alpha_pred alone.  The way out exists: ntx_trainer_composite_weights(t, weights_dev) registers a
+ * buffer weights_dev[N,S] (DEVICE) that every following step fills until it is taken back with NULL -- ntx_train_step_gradients (the coarse
+ * pass's use), and equally ntx_train_forward and ntx_train_forward_instanced.  An instanced forward writes (1 - el) T at the live samples and
+ * exactly 0 at samples that are not live and on rays with hit == 0; the appended sample's weight is not stored: it is
+ * alpha_pred - sum_s w_s, so a loss on it is expressible through alpha_pred.
+ * This entry is the way back: d_weights_dev[N,S] (DEVICE) = dL/d weights for the NEXT ntx_train_backward of the pending forward, plain or
+ * instanced.  The composite's adjoint (ray_adjoint, ntx_trainer.hip) has dL/dw_k = c_k + dA' with c_k = dC . rgb_k; with a direct term
+ * g_k = d_weights[ray][k] it is
+ *     dL/dw_k = c_k + g_k + dA',
+ * and the same division-free recurrences hold with c_k + g_k in the place of c_k: dL/da_i = T_i (dA' Z_i + ((c_i + g_i) - V_i)),
+ * V_{i-1} = (c_i + g_i) a_i + f_i V_i.  dL/d raw rgb is unchanged.  Everything behind the adjoint -- both backends, the weight gradients, the
+ * parameter and input gradients, the instanced folds -- takes the gradient of such a loss with no change.
+ * A plain ray without a live sample (tnear_far inf) selects 0 for its row, as for d_color / d_alpha: nothing of a row that may hold NaN or
+ * inf is multiplied.  An instanced step reads the buffer at live samples only, and nothing of a ray with hit == 0.
+ * The registration is consumed by that backward (used once); it is dropped by any new forward, by ntx_train_step_gradients, and by
+ * d_weights_dev = NULL.  A backward without one runs the code path, and leaves every bit, of a handle that never called this entry; the
+ * fused-loss step (ntx_train_step_gradients) takes no weight cotangent: its loss is its own.
+ * The entry only records the pointer: it takes no stream, waits for nothing, allocates nothing and launches nothing.  CONTRACT: the caller
+ * keeps d_weights_dev alive and unchanged until the backward's work on its stream has completed.
+ * NTX_E_INVALID: t NULL, or no forward pending.  NTX_E_UNSUPPORTED: an IPE handle (ntx_trainer_composite_weights refuses it too).
+ * Out of scope: IPE handles, coarse + fine, a stored weight for the appended sample, second order, an all-reduce of anything new. */
+int ntx_trainer_weight_cotangent(ntx_trainer *t, const float *d_weights_dev);
 
 #ifdef __cplusplus
 }

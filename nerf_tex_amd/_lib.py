@@ -173,6 +173,7 @@ SYMBOLS = {
     "ntx_trainer_sample_input_gradients": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "ntx_trainer_enable_gradients": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ntx_trainer_enable_instanced": (C.c_int, [_vp]),
+    "ntx_trainer_weight_cotangent": (C.c_int, [_vp, _vp]),
 }
 
 

@@ -15,6 +15,13 @@ With `input_gradients=True` / "only" on the trainer (either kind), `rays_o` / `r
 likewise (camera or pose refinement: the sample depths are constants), and the instanced op's `pts` / `rays_d_map` theirs; with it off, both ops
 do what they do without it.
 
+A loss that looks along the ray takes the compositing weights as a third differentiable output -- `DifferentiableRender(trainer,
+weights=True)` returns (color_pred, alpha_pred, weights [N, S]), and their cotangent reaches the composite's adjoint through
+`Trainer.backward(..., d_weights=)` (`ntx_trainer_weight_cotangent`):
+
+    color_pred, alpha_pred, weights = DifferentiableRender(trainer, weights=True)(rays_o, rays_d, t, parameters, cone_scale, z_vals=z)
+    (mse(color_pred, color) + 0.1 * mse(nerf_tex_amd.loss.expected_depth(weights, z), depth)).backward()
+
 One backward per forward (the activations are the trainer's, not the graph's), first order only: nothing differentiates the backward.  A
 data-parallel mean of the ranks' gradients is the gradient of their joint loss only when that loss is a mean over rays.  A coarse + fine
 pair is two passes with two sets of cotangents and is not taken.
@@ -28,14 +35,15 @@ import functools
 
 
 class DifferentiableRender:
-    def __init__(self, trainer) -> None:
+    def __init__(self, trainer, weights: bool = False) -> None:
         from .train import CoarseFineTrainer
         if isinstance(trainer, CoarseFineTrainer):
             raise TypeError("DifferentiableRender takes one pass (Trainer, FlexTrainer, BranchTrainer), not a coarse + fine pair")
-        self.trainer = trainer
+        self.trainer, self.weights = trainer, bool(weights)
 
     def __call__(self, rays_o, rays_d, t, parameters, cone_scale, **kw):
-        """`Trainer.forward`'s arguments; returns (color_pred [N,3], alpha_pred [N]) in the autograd graph."""
+        """`Trainer.forward`'s arguments; returns (color_pred [N,3], alpha_pred [N]) in the autograd graph -- with `weights=True` (color_pred,
+        alpha_pred, weights [N,S])."""
         import torch
         tr = self.trainer
         wants = isinstance(parameters, torch.Tensor) and parameters.requires_grad
@@ -46,7 +54,8 @@ class DifferentiableRender:
         anchor = torch.zeros((), device=torch.device("cuda", tr.device), requires_grad=True)
         # inputs that take a gradient reach the function as direct arguments: autograd does not look inside the tuple
         ins = [a if getattr(tr, "input_gradients", False) and isinstance(a, torch.Tensor) and a.requires_grad else None for a in (rays_o, rays_d)]
-        return _render_function().apply(anchor, parameters if wants else None, ins[0], ins[1], tr, (rays_o, rays_d, t, parameters, cone_scale), kw)
+        return _render_function().apply(anchor, parameters if wants else None, ins[0], ins[1], tr, (rays_o, rays_d, t, parameters, cone_scale),
+                                        dict(kw, return_weights=True) if self.weights else kw)
 
 
 class DifferentiableInstanceRender:
@@ -60,11 +69,13 @@ class DifferentiableInstanceRender:
     `params_map` (default: the tuple's) that requires grad receives the per-sample gradient (zero outside every patch); that needs
     `param_gradients` on.  The weight gradient stays in the trainer.  One backward per forward, as `DifferentiableRender`."""
 
-    def __init__(self, trainer, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True) -> None:
+    def __init__(self, trainer, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True, weights: bool = False) -> None:
         if not hasattr(trainer, "forward_instanced"):
             raise TypeError("DifferentiableInstanceRender takes one pass (FlexTrainer, BranchTrainer, or Trainer with instanced=True), not a coarse + fine pair")
         self.trainer = trainer
         self.opts = dict(patch_scale=float(patch_scale), density_scale=float(density_scale), density_reweighting=bool(density_reweighting))
+        if weights:                                                  # the third output: weights [N,S], 0 outside every patch (the appended sample's is not among them)
+            self.opts["return_weights"] = True
 
     def __call__(self, bufs, cone_scale, params_map=None, **kw):
         """`Trainer.forward_instanced`'s arguments (composite_bkgd, bkgd_color, hit in `kw`); returns (color_pred [N,3], alpha_pred [N]) in
@@ -96,23 +107,28 @@ def _render_function():
             if ctx.instanced:                                        # ("instanced", the instancer's ten buffers, cone_scale)
                 _, bufs, cone_scale = args
                 bufs = tuple(b.detach() if isinstance(b, torch.Tensor) else b for b in bufs)
-                color, alpha = trainer.forward_instanced(bufs, cone_scale, **kw)
+                outs = trainer.forward_instanced(bufs, cone_scale, **kw)
             else:
                 rays_o, rays_d, t, parameters, cone_scale = (a.detach() if isinstance(a, torch.Tensor) else a for a in args)
-                color, alpha = trainer.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
+                outs = trainer.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
             like = lambda x: None if x is None else (tuple(x.shape), x.device, x.dtype)
             ctx.trainer, ctx.serial, ctx.like, ctx.like_in = trainer, trainer._pending[0], like(held), (like(in_a), like(in_b))
-            return color, alpha
+            if len(outs) == 3:                                       # with the weights: an output the loss does not use hands back None, not zeros
+                ctx.set_materialize_grads(False)
+                ctx.color_like = like(outs[0])
+            return outs
 
         @staticmethod
         @torch.autograd.function.once_differentiable
-        def backward(ctx, d_color, d_alpha):
+        def backward(ctx, d_color, d_alpha, d_weights=None):
             tr = ctx.trainer
             pending = tr._pending
             if pending is None or pending[0] != ctx.serial:
                 raise RuntimeError("DifferentiableRender: one backward per forward -- this forward's step has been taken back already, or the trainer has "
                                    "run another step since (its activations are the trainer's, not the graph's)")
-            tr.backward(d_color, d_alpha)
+            if d_color is None:                                      # (only where the weights are an output: a loss of alpha_pred / the weights alone)
+                d_color = torch.zeros(ctx.color_like[0], device=ctx.color_like[1], dtype=ctx.color_like[2])
+            tr.backward(d_color, d_alpha) if d_weights is None else tr.backward(d_color, d_alpha, d_weights)
             grad = None
             if ctx.like is not None and ctx.instanced:
                 shape, device, dtype = ctx.like

@@ -757,8 +757,9 @@ int FlexBackend::activation(int layer, int64_t n_samples_total, float *out_host)
     else if (layer >= 48 && layer < 48 + (int)app.layers.size()) { const FlexLayer &l = app.layers[layer - 48]; from = l.Y; width = l.out; ld = l.ldy; }
     else if (layer == 64) { from = t->sigma; width = ld = 1; }
     else if (layer == 65) { from = t->raw_rgb; width = ld = 3; }
+    else if (layer == 30) { from = t->dgrad; width = ld = 4; }
     else return ntx_set_error(NTX_E_INVALID, "layer %d (0 .. %d: the ReLU layers in the order trunk, colour layers, colour half; 32 + j / 48 + j: layer j of the geometry / "
-                              "appearance branch, where the model has it; 64 the raw density, 65 the raw colour)", layer, (int)relu_layers.size() - 1);
+                              "appearance branch, where the model has it; 64 the raw density, 65 the raw colour, 30 the composite's adjoint)", layer, (int)relu_layers.size() - 1);
     TRAIN_TRY(hipSetDevice(t->device));
     TRAIN_TRY(hipDeviceSynchronize());
     TRAIN_TRY(hipMemcpy2D(out_host, (size_t)width * sizeof(float), from, (size_t)ld * sizeof(float), (size_t)width * sizeof(float), (size_t)n_samples_total, hipMemcpyDeviceToHost));

@@ -139,7 +139,8 @@ struct ntx_trainer {
     // ntx_train_forward's step until its ntx_train_backward: the caller's rays (alive and unchanged until then), what the composite was run with;
     // samples: the step is ntx_train_forward_instanced's, and smp holds the caller's buffers instead of rays
     struct Pending { bool open = false, samples = false; ntx_train::StepRays rays{}; ntx_train::StepSamples smp{}; uint32_t flags = 0; float bkgd[3] = {1.0f, 1.0f, 1.0f};
-                     const float *noise = nullptr; } pending;
+                     const float *noise = nullptr;
+                     const float *d_weights = nullptr; } pending;   // d_weights: ntx_trainer_weight_cotangent's [N][S] for the pending step's backward, or NULL
     ntx_train::Backend *backend = nullptr;
     ntx_train::DeviceMemory mem;               // (destroyed after the body below has run)
     ~ntx_trainer() { (void)hipSetDevice(device); delete backend; }

@@ -124,7 +124,10 @@ __device__ __forceinline__ void ray_composite(const CompositeArgs &a, int ray, i
 // sample (f_i -> 1e-10) loses the digits the forward product kept, and "dA' (1 - sum)" loses them again when the ray saturates BEHIND
 // sample i (round 5's kernel did both: profiles/r05/soak_train_seed3.txt, case 297).
 // A chunk of 64 samples is a suffix scan of the affine maps X -> b_i + f_i X (composed pairwise), carried from chunk to chunk back to front.
-__device__ __forceinline__ void ray_adjoint(const CompositeArgs &a, int ray, int lane, const float *el, const float *T, const float (&dC)[3], float dA) {
+// A loss on the weights themselves (gw = the ray's row of dL/d w, or NULL): dL/dw_k = c_k + g_k + dA', and everything above holds with
+// c_k + g_k in the place of c_k -- in c_i - V_i and in V_{i-1} = (c_i + g_i) a_i + f_i V_i; dL/d raw rgb = w dC rgb' has no such term.  With
+// gw NULL nothing is added (no + 0.0f): the fused step and a backward without a weight cotangent keep their bits.
+__device__ __forceinline__ void ray_adjoint(const CompositeArgs &a, int ray, int lane, const float *el, const float *T, const float (&dC)[3], float dA, const float *gw) {
     const int S = a.S;
     const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S, *rr = a.raw_rgb + (size_t)ray * S * 3;
     const float *nz = a.noise ? a.noise + (size_t)ray * S : nullptr;
@@ -138,6 +141,7 @@ __device__ __forceinline__ void ray_adjoint(const CompositeArgs &a, int ray, int
             e = el[s];
             for (int c = 0; c < 3; ++c) rgb[c] = rgb_of(rr[3 * s + c], a.map_exr);
             cs = (dC[0] * rgb[0] + dC[1] * rgb[1]) + dC[2] * rgb[2];
+            if (gw) cs += gw[s];
             F = e + 1e-10f; Bz = -1e-10f; Bv = cs * (1.0f - e);
         }
         // inclusive suffix composition: lane l ends with the maps of samples l .. 63 of the chunk composed, X_{l-1} = B + F X_63
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
         if (a.kind == NTX_LOSS_ALPHA) { float v; loss_term(a.alpha_loss_fn, a.alpha_true[ray], A, inv_a, v, dA); total += a.gamma * v; dA *= a.gamma; }   // :38
     }
     if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; a.ray_loss[ray] = total; }
-    ray_adjoint(a, ray, lane, el, T, dC, dA);
+    ray_adjoint(a, ray, lane, el, T, dC, dA, nullptr);
 }
 // ntx_train_forward's composite: (a) alone -- the predictions (and the weights a coarse pass hands on); nothing of the loss, no gradient
 __global__ __launch_bounds__(256) void composite_forward_kernel(CompositeArgs a) {
@@ -209,8 +213,10 @@ __global__ __launch_bounds__(256) void composite_forward_kernel(CompositeArgs a)
 // ntx_train_backward's composite: el and T again from what the pending forward left (sigma, dists, noise, raw_rgb), then (b) from the
 // caller's cotangents d_color [N][3] and d_alpha [N] (NULL: 0).  A ray whose depths are not finite has dists 0 throughout: it composites to
 // nothing, and its gradient is 0 whatever its cotangent holds (inf and NaN included) -- by selecting a zero cotangent for it, so that (b)
-// runs on the same numbers as with the cotangent zeroed by the caller, never by a product with what may not be finite.
-__global__ __launch_bounds__(256) void composite_adjoint_kernel(CompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha) {
+// runs on the same numbers as with the cotangent zeroed by the caller, never by a product with what may not be finite.  d_weights: NULL, or
+// [N][S] = dL/d weights (ntx_trainer_weight_cotangent); such a ray selects none of it either.
+__global__ __launch_bounds__(256) void composite_adjoint_kernel(CompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha,
+                                                                const float *__restrict__ d_weights) {
     __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0) zero_dhead_tail(a);
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(256) void composite_adjoint_kernel(CompositeArgs a,
     float dC[3];
     for (int c = 0; c < 3; ++c) dC[c] = live ? d_color[3 * ray + c] : 0.0f;
     const float dA = live && d_alpha ? d_alpha[ray] : 0.0f;
-    ray_adjoint(a, ray, lane, el, T, dC, dA);
+    ray_adjoint(a, ray, lane, el, T, dC, dA, live && d_weights ? d_weights + (size_t)ray * a.S : nullptr);
 }
 // ---------------------------------------------------------------------------------------------------------------------------
 // The instanced step (ntx_train_forward_instanced): InstanceRenderer.evaluate_model + map_model_output (renderer.py:247-354) with the
@@ -288,6 +294,7 @@ struct InstCompositeArgs {
     StepSamples s; const float *raw_rgb, *sigma;
     int map_exr, composite_bkgd; float bkgd[3];
     float *color, *alpha;                      // [N][3], [N]
+    float *weights;                            // NULL, or [N][S]: the forward's weights a_s T_s of the S samples (0 where a sample is not live, and on a ray with hit == 0)
     float *dgrad;                              // [n_live][4] in compact row order
 };
 // ray_transmittance for such a ray: el[s] = exp(-relu(sigma') dists / patch_scale), 1 where the sample is not live, and T[s]; the factors in
@@ -326,16 +333,22 @@ __global__ __launch_bounds__(256) void inst_composite_forward_kernel(InstComposi
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long ray = (long long)blockIdx.x * 4 + wave;
     if (ray >= p.n_rays) return;
-    if (!p.hit[ray]) { if (lane < 3) a.color[3 * ray + lane] = 0.0f; if (lane == 3) a.alpha[ray] = 0.0f; return; }
+    if (!p.hit[ray]) {
+        if (lane < 3) a.color[3 * ray + lane] = 0.0f;
+        if (lane == 3) a.alpha[ray] = 0.0f;
+        if (a.weights) for (int s = lane; s < p.S; s += 64) a.weights[ray * p.S + s] = 0.0f;
+        return;
+    }
     float *el = sh_a[wave], *T = sh_T[wave];
     const float T_last = inst_transmittance(a, ray, lane, el, T);
     float c[3] = {0.0f, 0.0f, 0.0f}, A = 0.0f;
     for (int s = lane; s < p.S; s += 64) {
         const int row = p.row_of[ray * p.S + s];
-        if (row < 0) continue;                                                                  // a = 0: no weight
+        if (row < 0) { if (a.weights) a.weights[ray * p.S + s] = 0.0f; continue; }             // a = 0: no weight
         const float w = (1.0f - el[s]) * T[s];
         for (int k = 0; k < 3; ++k) c[k] += w * rgb_of(a.raw_rgb[3 * (size_t)row + k], a.map_exr);
         A += w;
+        if (a.weights) a.weights[ray * p.S + s] = w;                                            // (the appended sample's is alpha_pred - sum_s w_s)
     }
     const float wl = p.alpha_last[ray] * T_last;                                                // the appended sample
     A = wave_sumf(A) + wl;
@@ -350,8 +363,10 @@ __global__ __launch_bounds__(256) void inst_composite_forward_kernel(InstComposi
 // carries start at V_{S-1} = (dC . color_last) alpha_last and Z_{S-1} = ((1 - alpha_last) + 1e-10) - 1e-10 instead of 0 and 1.  A sample
 // that is not live is the map X -> -1e-10 + (1 + 1e-10) X for Z and the identity's for V, and writes nothing.  dL/d sigma of a live sample:
 // d_a (dists / patch_scale) e alpha_weight density_scale where sigma' > 0.  A ray with hit == 0 has no live sample: nothing of it is
-// written whatever its cotangent holds, which is not even read.
-__global__ __launch_bounds__(256) void inst_composite_adjoint_kernel(InstCompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha) {
+// written whatever its cotangent holds, which is not even read.  d_weights: NULL, or [N][S] = dL/d weights of the S samples, read at live
+// samples only and added to c_k as in ray_adjoint (the appended sample has no stored weight and takes none).
+__global__ __launch_bounds__(256) void inst_composite_adjoint_kernel(InstCompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha,
+                                                                     const float *__restrict__ d_weights) {
     __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
     const StepSamples &p = a.s;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, S = p.S;
@@ -376,6 +391,7 @@ __global__ __launch_bounds__(256) void inst_composite_adjoint_kernel(InstComposi
             if (row >= 0) {
                 for (int c = 0; c < 3; ++c) rgb[c] = rgb_of(a.raw_rgb[3 * (size_t)row + c], a.map_exr);
                 cs = (dC[0] * rgb[0] + dC[1] * rgb[1]) + dC[2] * rgb[2];
+                if (d_weights) cs += d_weights[m];
             }
             F = e + 1e-10f; Bz = -1e-10f; Bv = row >= 0 ? cs * (1.0f - e) : 0.0f;
         }
@@ -517,6 +533,14 @@ int ntx_trainer_composite_weights(ntx_trainer *t, float *weights_dev) {
     t->weights_out = weights_dev;
     return NTX_OK;
 }
+int ntx_trainer_weight_cotangent(ntx_trainer *t, const float *d_weights_dev) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    if (t->ipe) return ntx_set_error(NTX_E_UNSUPPORTED, "an IPE trainer hands out no composite weights (ntx_trainer_composite_weights), so it takes no cotangent of them");
+    if (!t->pending.open) return ntx_set_error(NTX_E_INVALID, "no forward is pending: the weight cotangent belongs to the next ntx_train_backward of a pending ntx_train_forward / "
+                                               "ntx_train_forward_instanced");
+    t->pending.d_weights = d_weights_dev;                                                       // (NULL: none)
+    return NTX_OK;
+}
 namespace ntx_train {
 __global__ void add_kernel(float *__restrict__ dst, const float *__restrict__ src, long long n) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -614,7 +638,7 @@ static InstCompositeArgs inst_composite_args(const ntx_trainer *t, const StepSam
     c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.dgrad = t->dgrad;
     return c;
 }
-static int backward_instanced(ntx_trainer *t, const float *d_color, const float *d_alpha, hipStream_t st) {
+static int backward_instanced(ntx_trainer *t, const float *d_color, const float *d_alpha, const float *d_weights, hipStream_t st) {
     const StepSamples &s = t->pending.smp;
     if (t->pg_mode != 0 && !t->sample_pg && t->mem.alloc(&t->sample_pg, (size_t)t->cap * t->P) != NTX_OK) return t->mem.rc;
     if (t->ig_mode != 0 && !t->d_pts) {
@@ -622,7 +646,7 @@ static int backward_instanced(ntx_trainer *t, const float *d_color, const float 
         if (t->mem.rc != NTX_OK) return t->mem.rc;
     }
     const InstCompositeArgs c = inst_composite_args(t, s, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
-    if (s.n_live > 0) hipLaunchKernelGGL(inst_composite_adjoint_kernel, dim3((unsigned)((s.n_rays + 3) / 4)), dim3(256), 0, st, c, d_color, d_alpha);
+    if (s.n_live > 0) hipLaunchKernelGGL(inst_composite_adjoint_kernel, dim3((unsigned)((s.n_rays + 3) / 4)), dim3(256), 0, st, c, d_color, d_alpha, d_weights);
     int rc = t->backend->backward_samples(s, t->sample_pg, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
@@ -636,7 +660,7 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
                              const ntx_render_opts *opts, const float *z_vals, const float *color_true, const float *alpha_true, const ntx_loss_desc *loss,
                              float *color_pred, float *alpha_pred, float *loss_out, ntx_stream stream) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
-    t->pending.open = false;                                                                    // a forward left open is not this step's
+    t->pending.open = false; t->pending.d_weights = nullptr;                                    // a forward left open is not this step's, nor is its weight cotangent
     if (!color_true || !loss) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
     if (int rc = step_check(t, rays_o, rays_d, tnear_far, params, cone_scale, n_rays, n_samples, blur_idx, z_vals)) return rc;
     if (loss->size < sizeof(ntx_loss_desc) || (loss->kind != NTX_LOSS_NERF && loss->kind != NTX_LOSS_ALPHA) || (loss->loss_fn != NTX_LOSS_MSE && loss->loss_fn != NTX_LOSS_SMAPE) ||
@@ -666,7 +690,7 @@ int ntx_train_forward(ntx_trainer *t, const float *rays_o, const float *rays_d, 
                       const float *cone_scale, int64_t n_rays, int n_samples, int blur_idx, uint32_t flags, const float *bkgd, uint64_t perturb_seed,
                       const ntx_render_opts *opts, const float *z_vals, float *color_pred, float *alpha_pred, ntx_stream stream) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
-    t->pending.open = false;                                                                    // a new forward replaces the one left open
+    t->pending.open = false; t->pending.d_weights = nullptr;                                    // a new forward replaces the one left open (and drops its weight cotangent)
     if (int rc = step_check(t, rays_o, rays_d, tnear_far, params, cone_scale, n_rays, n_samples, blur_idx, z_vals)) return rc;
     StepRays rays{};
     const float *noise = nullptr;
@@ -686,13 +710,15 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
     if (!t->pending.open) return ntx_set_error(NTX_E_INVALID, "no ntx_train_forward is pending (one ntx_train_backward per forward; ntx_train_step_gradients closes it too)");
     if (!d_color) return ntx_set_error(NTX_E_INVALID, "d_color is NULL");
     t->pending.open = false;
+    const float *d_weights = t->pending.d_weights;                                              // ntx_trainer_weight_cotangent's, used once
+    t->pending.d_weights = nullptr;
     TRAIN_TRY(hipSetDevice(t->device));
-    if (t->pending.samples) return backward_instanced(t, d_color, d_alpha, (hipStream_t)stream);
+    if (t->pending.samples) return backward_instanced(t, d_color, d_alpha, d_weights, (hipStream_t)stream);
     const StepRays &rays = t->pending.rays;
     CompositeArgs c = composite_args(t, rays, t->pending.noise, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
     c.weights = nullptr;                                                                        // (b) alone: nothing of the forward is written again
     t->step_noise = t->pending.noise;
-    hipLaunchKernelGGL(composite_adjoint_kernel, dim3((unsigned)((rays.n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c, d_color, d_alpha);
+    hipLaunchKernelGGL(composite_adjoint_kernel, dim3((unsigned)((rays.n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c, d_color, d_alpha, d_weights);
     int rc = t->backend->backward(rays, (hipStream_t)stream);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
@@ -706,7 +732,7 @@ int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const f
                                 int n_samples, int blur_idx, float patch_scale, float density_scale, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred,
                                 int64_t *n_live_out, ntx_stream stream) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
-    t->pending.open = false;                                                                    // a new forward of either kind replaces the one left open
+    t->pending.open = false; t->pending.d_weights = nullptr;                                    // a new forward of either kind replaces the one left open
     if (int rc = t->backend->takes_samples()) return rc;
     if (!rays_d_map || !pts || !dists || !color_last || !alpha_last || !hit || (t->P > 0 && !params_map)) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
     if (n_samples < 1 || n_samples > MAX_TRAIN_SAMPLES) return ntx_set_error(NTX_E_INVALID, "n_samples outside 1 .. %d", MAX_TRAIN_SAMPLES);
@@ -732,7 +758,8 @@ int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const f
                   d.dir_freq, d.param_freq, patch_scale, density_scale, t->live, t->row_of, n_live};
     int rc = t->backend->forward_samples(s, st);
     if (rc != NTX_OK) return rc;
-    const InstCompositeArgs c = inst_composite_args(t, s, flags, bkgd, color_pred, alpha_pred);
+    InstCompositeArgs c = inst_composite_args(t, s, flags, bkgd, color_pred, alpha_pred);
+    c.weights = t->weights_out;                                                                 // ntx_trainer_composite_weights: [N][S], the forward alone writes them
     hipLaunchKernelGGL(inst_composite_forward_kernel, dim3(ray_grid), dim3(256), 0, st, c);
     TRAIN_TRY(hipGetLastError());
     t->pending.smp = s; t->pending.flags = flags; t->pending.noise = nullptr; t->pending.samples = true;

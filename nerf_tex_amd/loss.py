@@ -8,7 +8,9 @@ Same names, same constructor keywords: a training config's `loss_config` ({'modu
 Any OTHER loss is written in PyTorch: `Trainer.gradients_step`, `Train` and `ParameterFitter.fit` take an object without `desc()` as a callable
 `loss(color_true=, alpha_true=, color_pred=, alpha_pred=) -> scalar tensor` (the reference's call, loss.py:12, 30; a `loss_config` names its
 class by module path) and run the step as `ntx_train_forward`, the loss and its two cotangents in torch, `ntx_train_backward`
-(`nerf_tex_amd.autograd` is the same as a differentiable op)."""
+(`nerf_tex_amd.autograd` is the same as a differentiable op).  A callable whose signature also names `weights` (and `z_vals`) is a loss ALONG
+the ray: it receives the compositing weights [N, S] (and the step's depths) and its gradient at the weights goes back through
+`ntx_trainer_weight_cotangent`; `expected_depth` below is the helper such a loss starts from."""
 
 from __future__ import annotations
 
@@ -55,3 +57,13 @@ class AlphaLoss(NerfLoss):
         self.kind, self.loss_fn = _lib.LOSS_ALPHA, _fn(loss_fn)
         self.alpha_loss_fn = self.loss_fn if alpha_loss_fn is None else _fn(alpha_loss_fn)
         self.gamma, self.filter_color_loss, self.use_hard_mask = gamma, filter_color_loss, use_hard_mask
+
+
+def expected_depth(weights, z_vals):
+    """The depth a ray's composite expects: sum_s w_s z_s over the compositing weights `weights` [N, S] (`Trainer.forward(...,
+    return_weights=True)`, `DifferentiableRender(trainer, weights=True)`) and the sample depths `z_vals` [N, S] -- a torch expression, so a
+    loss built on it reaches the network through `backward(..., d_weights=)`.  A ray's samples that are not finite (a ray that misses the
+    proxy: depths inf, weights 0) count 0, not 0 * inf."""
+    import torch
+    z = torch.as_tensor(z_vals, device=weights.device, dtype=weights.dtype)
+    return (weights * torch.where(torch.isfinite(z), z, torch.zeros_like(z))).sum(-1)

@@ -22,7 +22,10 @@ fits parameters to target images with it.  The fused chain takes the same two ke
 `ntx_trainer_enable_gradients`), and `trainer_for(model, ..., fused=True)` keeps such a model on it when a gradient is asked for.
 The losses of `nerf_tex_amd.loss` are evaluated inside the step; any other loss is a callable on
 torch tensors, and the step runs as `forward(...)`, the loss and its two cotangents in torch, `backward(d_color, d_alpha)`
-(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op).  Every trainer also takes the step through
+(`nerf_tex_amd.autograd.DifferentiableRender`: the same pair as a differentiable op).  A loss that looks ALONG the ray -- an expected depth
+(`nerf_tex_amd.loss.expected_depth`), an entropy or distortion term -- takes the compositing weights too: `forward(..., return_weights=True)`
+hands them out, `backward(d_color, d_alpha, d_weights)` takes their cotangent (`ntx_trainer_weight_cotangent`), and a callable loss that
+names `weights` (and `z_vals`) in its signature receives them.  Every trainer also takes the step through
 the INSTANCED render (`forward_instanced(bufs, ...)` on an instancer's buffers, then the same `backward`; `DifferentiableInstanceRender`):
 the layer-by-layer ones as they are, the fused chain for a FourierFeatures model once asked (`instanced=True`, `enable_instanced()`)."""
 
@@ -74,7 +77,7 @@ class Trainer:
         self.n_weights = self._n_native if self._pad is None else int(self._pad.size)
         self._calls = 0
         self._last_rays = 0
-        self._pending, self._forwards = None, 0                                 # (serial, rays, device tensors) of a `forward` whose `backward` has not run
+        self._pending, self._forwards = None, 0                                 # (serial, rays, device tensors, samples a ray) of a `forward` whose `backward` has not run
         self.param_gradients = self.input_gradients = False
         if param_gradients is not False or input_gradients is not False:
             self.set_gradients(param_gradients, input_gradients)
@@ -223,7 +226,8 @@ class Trainer:
         background and counts in the loss, renderer.py:58-86), parameters [rows,P],
         cone_scale [N] or [N,1], color_true [N,3], alpha_true [N]; `loss`: a nerf_tex_amd.loss object (the fused step), or any callable
         `loss(color_true=, alpha_true=, color_pred=, alpha_pred=)` on torch tensors that returns a scalar (`forward`, torch, `backward`: the same
-        gradients for ANY differentiable loss of the predictions).  Returns (loss [1], color_pred [N,3],
+        gradients for ANY differentiable loss of the predictions; a callable whose signature names `weights` also receives the compositing
+        weights [N,S], and -- if it names `z_vals` too -- the step's depths [N,S]: a loss along the ray).  Returns (loss [1], color_pred [N,3],
         alpha_pred [N]) as GPU tensors; the gradients stay in the trainer.  `z_vals` [N, n_samples]: given sample depths (`n_samples` of them,
         default the trainer's) instead of the ones placed between t.  An IPE trainer (MipRenderer): parameters [rows, P + 1] with the blur parameter
         at blur_idx, `z_vals` [N, n_samples + 1] segment edges."""
@@ -277,37 +281,66 @@ class Trainer:
         return n, head, tail, (rays_o, rays_d, t, parameters, cone_scale, z_vals)
 
     def forward(self, rays_o, rays_d, t, parameters, cone_scale, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.), seed: Optional[int] = None, z_vals=None,
-                rays_per_param_row: int = 1, n_samples: Optional[int] = None):
+                rays_per_param_row: int = 1, n_samples: Optional[int] = None, return_weights: bool = False):
         """The first half of a step under any loss (`ntx_train_forward`): `gradients_step`'s arguments less the targets and the loss; returns
         (color_pred [N,3], alpha_pred [N]) as GPU tensors -- bit for bit `gradients_step`'s -- and leaves the step pending until
         `backward(d_color, d_alpha)`.  The trainer keeps the batch's device tensors until then; a tensor handed in that is already float32,
-        contiguous and on the device is read in place and must not be written before the backward."""
+        contiguous and on the device is read in place and must not be written before the backward.  `return_weights`: returns (color_pred,
+        alpha_pred, weights [N, S]) -- the composite's weights a_s T_s, for a loss that looks along the ray (`backward(..., d_weights=)`); an
+        IPE trainer hands out none (NTX_E_UNSUPPORTED)."""
         import torch
         dev, _, ptr = self._device_tools()
         self._pending = None
         n, head, tail, keep = self._step_inputs(rays_o, rays_d, t, parameters, cone_scale, composite_bkgd, bkgd_color, seed, z_vals, rays_per_param_row, n_samples)
+        S = int(n_samples or self.n_samples)
         color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev)
-        with torch.cuda.device(dev):
+        weights = torch.empty((n, S), device=dev) if return_weights else None
+        with torch.cuda.device(dev), self._weights_into(weights):
             _lib.check(_lib.lib.ntx_train_forward(self._h, *head, *tail, ptr(color), ptr(alpha), torch.cuda.current_stream(dev).cuda_stream))
         self._forwards += 1
-        self._pending = (self._forwards, n, keep)
-        return color, alpha
+        self._pending = (self._forwards, n, keep, S)
+        return (color, alpha, weights) if return_weights else (color, alpha)
 
-    def backward(self, d_color, d_alpha=None) -> None:
+    def _weights_into(self, weights):
+        """A context in which the forward fills `weights` [N, S] (`ntx_trainer_composite_weights`, taken back on the way out); None: nothing."""
+        import contextlib
+        if weights is None:
+            return contextlib.nullcontext()
+
+        @contextlib.contextmanager
+        def registered():
+            _lib.check(_lib.lib.ntx_trainer_composite_weights(self._h, weights.data_ptr()))
+            try:
+                yield
+            finally:
+                _lib.check(_lib.lib.ntx_trainer_composite_weights(self._h, None))
+        return registered()
+
+    def backward(self, d_color, d_alpha=None, d_weights=None) -> None:
         """The second half (`ntx_train_backward`): `d_color` [N,3] = dL/d color_pred and `d_alpha` [N] = dL/d alpha_pred (None: 0) of the pending
         `forward` -> the gradients of L, left in the trainer exactly as `gradients_step` leaves them (`gradients()`, `sync_gradients`,
         `apply_gradients`, `parameter_gradients()`).  One backward per forward: NTX_E_INVALID without a pending forward, or after a
         `gradients_step` in between.  Every gradient is linear in the two cotangents, so L is any differentiable function of the predictions;
-        a data-parallel mean of gradients (`sync_gradients`) is the gradient of the ranks' joint loss only if L is a mean over rays."""
+        a data-parallel mean of gradients (`sync_gradients`) is the gradient of the ranks' joint loss only if L is a mean over rays.
+        `d_weights` [N, S] = dL/d weights of the pending forward's compositing weights (`return_weights=True`; None: no such term, and the
+        backward is bit for bit what it is without the keyword): registered for this backward alone (`ntx_trainer_weight_cotangent`)."""
         import torch
         dev, to, ptr = self._device_tools()
         pending, self._pending = self._pending, None
-        d_color, d_alpha = to(d_color), to(d_alpha)
+        d_color, d_alpha, d_weights = to(d_color), to(d_alpha), to(d_weights)
         if pending is not None and d_color is not None:
             n = pending[1]
             if d_color.numel() != 3 * n or (d_alpha is not None and d_alpha.numel() != n):
                 self._pending = pending
                 raise ValueError(f"d_color / d_alpha hold {d_color.numel()} / {None if d_alpha is None else d_alpha.numel()} floats, the pending forward has {n} rays")
+            if d_weights is not None and d_weights.numel() != n * pending[3]:
+                self._pending = pending
+                raise ValueError(f"d_weights holds {d_weights.numel()} floats, the pending forward has {n} rays x {pending[3]} samples")
+        if d_weights is not None and d_color is not None:
+            rc = _lib.lib.ntx_trainer_weight_cotangent(self._h, ptr(d_weights))
+            if rc != _lib.NTX_OK:
+                self._pending = pending
+                _lib.check(rc)
         with torch.cuda.device(dev):
             rc = _lib.lib.ntx_train_backward(self._h, d_color.data_ptr() if d_color is not None else None, ptr(d_alpha), torch.cuda.current_stream(dev).cuda_stream)
         if rc != _lib.NTX_OK and d_color is None:
@@ -321,15 +354,49 @@ class Trainer:
         import torch
         _, to, _ = self._device_tools()
         color_true, alpha_true = to(color_true), to(alpha_true)
-        color, alpha = self.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
-        c, a = color.detach().requires_grad_(True), alpha.detach().requires_grad_(True)
+        names = _loss_keywords(loss)
+        if "weights" not in names:                                             # a loss of the predictions alone: today's call
+            color, alpha = self.forward(rays_o, rays_d, t, parameters, cone_scale, **kw)
+            c, a = color.detach().requires_grad_(True), alpha.detach().requires_grad_(True)
+            with torch.enable_grad():
+                val = loss(color_true=color_true, alpha_true=alpha_true, color_pred=c, alpha_pred=a)
+                if not isinstance(val, torch.Tensor) or val.numel() != 1:
+                    raise TypeError("a loss without desc() must return a scalar tensor")
+                d_color, d_alpha = torch.autograd.grad(val.reshape(()), (c, a), allow_unused=True)
+            self.backward(torch.zeros_like(color) if d_color is None else d_color, d_alpha)
+            return val.detach().reshape(1), color, alpha
+        # a loss along the ray: it names `weights`, and -- where it also names `z_vals` -- receives the step's depths, placed here exactly as the
+        # step would place them (`ntx_sample_depths` under the step's flags and seed) and handed to the forward as z_vals
+        more = {}
+        if "z_vals" in names:
+            if kw.get("z_vals") is None:
+                kw = dict(kw, z_vals=self._sample_depths(t, kw.get("seed"), kw.get("n_samples")), seed=self._calls if kw.get("seed") is None else kw.get("seed"))
+            more["z_vals"] = to(kw["z_vals"])
+        color, alpha, weights = self.forward(rays_o, rays_d, t, parameters, cone_scale, return_weights=True, **kw)
+        c, a, w = (x.detach().requires_grad_(True) for x in (color, alpha, weights))
         with torch.enable_grad():
-            val = loss(color_true=color_true, alpha_true=alpha_true, color_pred=c, alpha_pred=a)
+            val = loss(color_true=color_true, alpha_true=alpha_true, color_pred=c, alpha_pred=a, weights=w, **more)
             if not isinstance(val, torch.Tensor) or val.numel() != 1:
                 raise TypeError("a loss without desc() must return a scalar tensor")
-            d_color, d_alpha = torch.autograd.grad(val.reshape(()), (c, a), allow_unused=True)
-        self.backward(torch.zeros_like(color) if d_color is None else d_color, d_alpha)
+            d_color, d_alpha, d_weights = torch.autograd.grad(val.reshape(()), (c, a, w), allow_unused=True)
+        self.backward(torch.zeros_like(color) if d_color is None else d_color, d_alpha, d_weights)
         return val.detach().reshape(1), color, alpha
+
+    def _sample_depths(self, t, seed, n_samples):
+        """The depths [N, S] the next step would place between `t` under the trainer's `perturb` and `seed` (default: the step counter), as a
+        device tensor: `ntx_sample_depths`, the entry the step itself calls -- a step handed these as `z_vals` is that step bit for bit."""
+        import torch
+        dev, to, ptr = self._device_tools()
+        t = to(t)
+        n, S = t.reshape(-1, 2).shape[0], int(n_samples or self.n_samples)
+        if self.mip:
+            raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "an IPE trainer hands out no composite weights, so a loss on them has no depths to take")
+        z = torch.empty((n, S), device=dev)
+        seed = self._calls if seed is None else seed
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.ntx_sample_depths(ptr(t), n, S, _lib.FLAG_PERTURB if self.perturb else 0, int(seed) & (2 ** 64 - 1), None, ptr(z),
+                                                  torch.cuda.current_stream(dev).cuda_stream))
+        return z
 
     def set_gradients(self, param_gradients=False, input_gradients=False) -> None:
         """Both gradient modes for the following steps, each False / True / "only" (`ntx_trainer_enable_gradients`; the buffers are placed
@@ -394,7 +461,7 @@ class Trainer:
         return self._device_copies((p, d), (int(n.value), int(s.value), 3))
 
     def forward_instanced(self, bufs, cone_scale, *, patch_scale: float, density_scale: float = 1.0, density_reweighting: bool = True, composite_bkgd: bool = False,
-                          bkgd_color=(1., 1., 1.), hit=None):
+                          bkgd_color=(1., 1., 1.), hit=None, return_weights: bool = False):
         """The first half of a step on the INSTANCED render (`ntx_train_forward_instanced`): InstanceRenderer's tail (renderer.py:247-354) with
         every activation kept, the network on the in-patch samples alone.  `bufs`: the ten-tuple of an instancer's `get_model_input` --
         rays_d_map [N,S,3], pts [N,S,3], t [N,S], dists [N,S], color_last [N,1,3], alpha_last [N,1], alpha_weight [N,S], instance_id (unused),
@@ -402,7 +469,9 @@ class Trainer:
         instancer's `last_hit`) takes the place of idxs.  `cone_scale` [N] (read with blur_idx only).  Returns (color_pred [N,3], alpha_pred
         [N]) as GPU tensors and leaves the step pending until `backward(d_color, d_alpha)`, exactly as `forward` does; `self.last_live` is
         the number of in-patch samples the network ran on (reading it back is the step's one synchronisation).  Float32, contiguous device
-        tensors are read in place and must not be written before the backward."""
+        tensors are read in place and must not be written before the backward.  `return_weights`: returns (color_pred, alpha_pred, weights
+        [N, S]) -- (1 - el) T at the in-patch samples, exactly 0 elsewhere and on rays that hit nothing; the appended sample's weight is
+        alpha_pred - weights.sum(-1) -- for `backward(..., d_weights=)`."""
         import numpy as np
         import torch
         dev, to, ptr = self._device_tools()
@@ -426,7 +495,8 @@ class Trainer:
         flags = (_lib.FLAG_MAP_EXR if self.map_exr else 0) | (_lib.FLAG_COMPOSITE_BKGD if composite_bkgd else 0)
         color = torch.empty((n, 3), device=dev); alpha = torch.empty((n,), device=dev)
         live = C.c_int64(0)
-        with torch.cuda.device(dev):
+        weights = torch.empty((n, S), device=dev) if return_weights else None
+        with torch.cuda.device(dev), self._weights_into(weights):
             _lib.check(_lib.lib.ntx_train_forward_instanced(
                 self._h, ptr(keep["rd"]), ptr(keep["pts"]), ptr(keep["t"]), ptr(dists), ptr(keep["cl"]), ptr(keep["al"]), ptr(keep["aw"]), ptr(hit), ptr(keep["pm"]),
                 ptr(keep["cone"]), n, S, -1 if self.blur_idx is None else int(self.blur_idx), float(patch_scale), float(density_scale), flags, _lib.f3(bkgd_color),
@@ -434,8 +504,8 @@ class Trainer:
         self.last_live = int(live.value)
         self._last_rays = n
         self._forwards += 1
-        self._pending = (self._forwards, n, keep)
-        return color, alpha
+        self._pending = (self._forwards, n, keep, S)
+        return (color, alpha, weights) if return_weights else (color, alpha)
 
     def sample_parameter_gradients(self):
         """dL/d params_map of the last INSTANCED step: a torch tensor [N, S, P] on the trainer's device (geometry columns first, exact zeros at
@@ -564,10 +634,11 @@ class FlexTrainer(Trainer):
 
     def activation(self, layer: int, n_samples_total: int):
         """What the last step kept: `layer` 0 .. n_relu - 1 the output of the k-th ReLU layer (trunk 0 .. depth-1, colour hidden layers, colour
-        half layer), 64 the raw density, 65 the raw colour: [n_samples_total, width] float32 (tests)."""
+        half layer), 64 the raw density, 65 the raw colour, 30 the composite's adjoint (dL/d raw colour, dL/d raw density): [n_samples_total,
+        width] float32 (tests)."""
         import numpy as np
         widths = self.relu_widths()
-        width = {64: 1, 65: 3}.get(int(layer)) or (widths[int(layer)] if 0 <= int(layer) < len(widths) else 1)
+        width = {64: 1, 65: 3, 30: 4}.get(int(layer)) or (widths[int(layer)] if 0 <= int(layer) < len(widths) else 1)
         out = np.empty((int(n_samples_total), width), np.float32)
         _lib.check(_lib.lib.ntx_trainer_activation(self._h, int(layer), int(n_samples_total), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
@@ -775,6 +846,16 @@ class CoarseFineTrainer:
                                                 flat("color", 3), alpha, loss, composite_bkgd=composite_bkgd, bkgd_color=bkgd_color, seed=seed, rays_per_param_row=R)
         self.apply_gradients()
         return {"loss": val, "color_pred": c.reshape(B, R, 3), "alpha_pred": a.reshape(B, R), "color_pred_coarse": cc.reshape(B, R, 3), "alpha_pred_coarse": ac.reshape(B, R)}
+
+
+def _loss_keywords(loss) -> set:
+    """The keyword names a callable loss's signature spells out (a loss that takes **kwargs names none: it gets the reference's call)."""
+    import inspect
+    try:
+        params = inspect.signature(loss).parameters.values()
+    except (TypeError, ValueError):
+        return set()
+    return {p.name for p in params if p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)}
 
 
 def _is_mip(renderer_config) -> bool:
