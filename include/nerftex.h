@@ -721,10 +721,10 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
  * every weight gradient is exactly 0 and no contraction is launched.  A step's gradients do not depend on the trainer's capacity.
  * The step is then PENDING as ntx_train_forward's, under the same CONTRACT: the caller keeps all buffers alive and unchanged until
  * ntx_train_backward(t, d_color, d_alpha, stream) -- one backward per forward; a new forward of either kind or an ntx_train_step_gradients
- * replaces a pending one; a NULL d_color leaves it pending.  The backward: ray_adjoint's recurrences with the appended sample behind sample
- * S - 1 (the carries start at V = (dC . color_last) alpha_last, Z = ((1 - alpha_last) + 1e-10) - 1e-10); dL/d sigma of a live sample =
- * d_a * (dists / patch_scale) * e * alpha_weight * density_scale where sigma' > 0; color_last, alpha_last and alpha_weight take no gradient;
- * positions and directions take theirs under ntx_trainer_enable_input_gradients (ntx_trainer_sample_input_gradients).
+ * replaces a pending one; a NULL d_color leaves it pending.  The backward: ray_adjoint's recurrences through the view of an
+ * instanced ray (InstancedRay, ntx_composite.h: the appended sample behind sample S - 1, dL/d sigma of a live sample); color_last,
+ * alpha_last and alpha_weight take no gradient; positions and directions take theirs under ntx_trainer_enable_input_gradients
+ * (ntx_trainer_sample_input_gradients).
  * dL/d params (ntx_trainer_enable_param_gradients mode 1 / 2, semantics unchanged): an instanced step leaves PER-SAMPLE gradients
  * grad_dev[N][S][P] (geometry columns first; through FourierFeatures and, for blur_idx, times cone_scale * t / patch_scale; exact zeros at
  * samples that are not live) behind ntx_trainer_sample_param_gradients (DEVICE memory of the trainer, valid until the next step;
@@ -819,8 +819,8 @@ int ntx_trainer_enable_instanced(ntx_trainer *t);
  * exactly 0 at samples that are not live and on rays with hit == 0; the appended sample's weight is not stored: it is
  * alpha_pred - sum_s w_s, so a loss on it is expressible through alpha_pred.
  * This entry is the way back: d_weights_dev[N,S] (DEVICE) = dL/d weights for the NEXT ntx_train_backward of the pending forward, plain or
- * instanced.  The composite's adjoint (ray_adjoint, ntx_trainer.hip) has dL/dw_k = c_k + dA' with c_k = dC . rgb_k; with a direct term
- * g_k = d_weights[ray][k] it is
+ * instanced.  The composite's adjoint (ray_adjoint, ntx_composite.h: one statement for both kinds of step) has dL/dw_k = c_k + dA' with
+ * c_k = dC . rgb_k; with a direct term g_k = d_weights[ray][k] it is
  *     dL/dw_k = c_k + g_k + dA',
  * and the same division-free recurrences hold with c_k + g_k in the place of c_k: dL/da_i = T_i (dA' Z_i + ((c_i + g_i) - V_i)),
  * V_{i-1} = (c_i + g_i) a_i + f_i V_i.  dL/d raw rgb is unchanged.  Everything behind the adjoint -- both backends, the weight gradients, the

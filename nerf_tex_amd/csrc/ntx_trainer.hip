@@ -4,20 +4,18 @@
 // network: composite_loss_kernel (renderer.py:170-213 per ray, the ray's term of the loss and the adjoint of both), reduce_batch_kernel (the
 // weight gradients' partial sums added in a fixed order: a step is bit-reproducible), adam_kernel (train.py:49-52).  The same step cut in
 // two at the predictions, for a loss the caller evaluates (ntx_train_forward / ntx_train_backward): composite_forward_kernel and
-// composite_adjoint_kernel, made of the device pieces composite_loss_kernel is made of.  And the same pair for the instanced render
-// (ntx_train_forward_instanced: InstanceRenderer's tail, renderer.py:247-354): the compaction of the in-patch samples (live_*_kernel),
-// inst_composite_forward_kernel and inst_composite_adjoint_kernel, the network on the compact rows.
+// composite_adjoint_kernel.  And the same pair for the instanced render (ntx_train_forward_instanced: InstanceRenderer's tail,
+// renderer.py:247-354): the compaction of the in-patch samples (live_*_kernel), inst_composite_forward_kernel and
+// inst_composite_adjoint_kernel, the network on the compact rows.  All five composite kernels are made of the device pieces of
+// ntx_composite.h -- ray_transmittance, ray_forward, ray_adjoint, each formula once -- over a view of the ray (WholeRay / InstancedRay).
 // The network between the encoded rays and the composite is a backend's (ntx_trainer.h): the 8 x 256 chain of ntx_backend_chain.hip behind
 // ntx_trainer_create, the layer-by-layer step of ntx_backend_flex.hip behind ntx_trainer_create_flex / _flex_ex.  Inference fuses the whole network into
 // one kernel because nothing of it has to survive (ntx_device.h); a training step has to keep every layer's activations for the weight
 // gradients, and with 288 GB of HBM they are simply stored, once each.  Everything is float32 with float32 accumulation, like the
 // reference's TensorFlow graph.  gfx950 only.
 #include <cmath>
-#include "ntx_trainer.h"
-#include "ntx_encode.h"   // o_index
-#include "ntx_device.h"   // f32x4
+#include "ntx_composite.h"
 namespace ntx_train {
-using ntx::f32x4;
 __global__ void reduce_batch_kernel(ReduceBatch b) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     int j = 0;
@@ -42,25 +40,10 @@ void launch_reduce(hipStream_t st, const ReduceBatch &b) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// map_model_output (renderer.py:170-213) per ray, the ray's terms of the loss (loss.py: both losses are means over the rays, so a ray's
-// gradient needs nothing of the others) and the adjoint of both; wave per ray, lane l holds samples l, l + 64, ...
+// The five composite kernels: 256 threads, a wave per ray, the wave's el and T in two LDS rows.  Each formula is ntx_composite.h's, stated
+// there once for a whole ray (WholeRay: map_model_output, renderer.py:170-213) and a ray of an instanced step (InstancedRay:
+// renderer.py:318-354); a kernel keeps what is its own.
 // ---------------------------------------------------------------------------------------------------------------------------
-struct CompositeArgs {
-    const float *raw_rgb, *sigma, *dists;      // [N][S][3], [N][S], [N][S]
-    const float *noise;                        // NULL, or [N][S]: raw_noise_std * N(0,1), added to the density before its ReLU (renderer.py:190-195)
-    int n_rays, S, map_exr, composite_bkgd; float bkgd[3];
-    const float *color_true, *alpha_true;
-    int kind, loss_fn, alpha_loss_fn, filter_color_loss, use_hard_mask; float gamma;
-    float *color, *alpha, *ray_loss;           // [N][3], [N], [N]: the predictions and each ray's share of the loss
-    float *weights;                            // NULL, or [N][S]: the composite's weights a_i T_i (what the importance sampler takes, renderer.py:127-128)
-    float *dgrad;                              // [M][4]: dL/d raw rgb, dL/d sigma per sample (the way back starts from these)
-    float *dhead;                              // the same as one O-layout tile per block of 32 samples (rows 0-2, 3): the narrow heads' dY
-    long long M;
-};
-__device__ __forceinline__ float rgb_of(float raw, int map_exr) {
-    if (map_exr) return raw > 0.0f ? raw + 1.0f : expf(raw);                                   // elu + 1 (:184-185)
-    return 1.0f / (1.0f + expf(-raw));                                                         // sigmoid (:187)
-}
 __device__ __forceinline__ void loss_term(int fn, float t, float p, float inv_n, float &value, float &grad) {
     if (fn == NTX_LOSS_MSE) { const float e = t - p; value = e * e * inv_n; grad = -2.0f * e * inv_n; }          // loss.py:51-54
     else {                                                                                                        // smape, eps 1e-2 (:56-59)
@@ -69,169 +52,103 @@ __device__ __forceinline__ void loss_term(int fn, float t, float p, float inv_n,
         value = ae / den * inv_n; grad = (-sgn / den - ae / (den * den)) * inv_n;
     }
 }
-__device__ __forceinline__ size_t dhead_at(long long m, int row) { return o_index(m >> 5, 1, row, (int)(m & 31)); }
 // the tail of the last block of 32 samples: no gradient (the threads of one workgroup)
 __device__ __forceinline__ void zero_dhead_tail(const CompositeArgs &a) {
     const long long end = (a.M + 31) / 32 * 32;
     for (long long m = a.M + threadIdx.x; m < end; m += 256)
         for (int r = 0; r < 4; ++r) a.dhead[dhead_at(m, r)] = 0.0f;
 }
-// Piece (a) of a ray, first half: el[s] = exp(-relu(sigma) dist) and T[s], the exclusive running product, in the wave's two LDS rows.
-__device__ __forceinline__ void ray_transmittance(const CompositeArgs &a, int ray, int lane, float *el, float *T) {
-    const int S = a.S;
-    const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S;
-    const float *nz = a.noise ? a.noise + (size_t)ray * S : nullptr;
-    // el[s] = exp(-relu(sigma) dist): a_s = 1 - el[s] (:195), and the factor of the running product, (1 - a_s) + 1e-10 (:198), is taken as
-    // el[s] + 1e-10 -- the value of the reference's expression without the float32 round trip through 1 - (1 - e), which on a saturated sample
-    // (e ~ 1e-6) leaves 1 - a with two digits: the ray's transmittance, and with it every gradient behind the sample, would carry that error
-    for (int s = lane; s < S; s += 64) { const float v = nz ? sg[s] + nz[s] : sg[s]; const float r = v > 0.0f ? v : 0.0f; el[s] = expf(-r * ds[s]); }    // :190-195
-    __builtin_amdgcn_wave_barrier();
-    // exclusive running product of (1 - a) + 1e-10, sequential like tf.math.cumprod (:198): chunks of 64 with a carry
-    float carry = 1.0f;
-    for (int s0 = 0; s0 < S; s0 += 64) {
-        const int s = s0 + lane;
-        float f = s < S ? el[s] + 1e-10f : 1.0f, incl = f;
-        for (int o = 1; o < 64; o <<= 1) { const float w = __shfl_up(incl, o); if (lane >= o) incl *= w; }
-        float excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = 1.0f;
-        if (s < S) T[s] = carry * excl;
-        carry *= __shfl(incl, 63);
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-// Piece (a), second half: the ray's colour and opacity from el and T (every lane ends with them), and the optional weights a_i T_i.
-__device__ __forceinline__ void ray_composite(const CompositeArgs &a, int ray, int lane, const float *el, const float *T, float &c0, float &c1, float &c2, float &A) {
-    const int S = a.S;
-    const float *rr = a.raw_rgb + (size_t)ray * S * 3;
-    c0 = 0.0f; c1 = 0.0f; c2 = 0.0f; A = 0.0f;
-    for (int s = lane; s < S; s += 64) {
-        const float w = (1.0f - el[s]) * T[s];
-        c0 += w * rgb_of(rr[3 * s], a.map_exr); c1 += w * rgb_of(rr[3 * s + 1], a.map_exr); c2 += w * rgb_of(rr[3 * s + 2], a.map_exr);
-        A += w;
-        if (a.weights) a.weights[(size_t)ray * S + s] = w;
-    }
-    c0 = wave_sumf(c0); c1 = wave_sumf(c1); c2 = wave_sumf(c2); A = wave_sumf(A);
-    if (a.composite_bkgd) { c0 += (1.0f - A) * a.bkgd[0]; c1 += (1.0f - A) * a.bkgd[1]; c2 += (1.0f - A) * a.bkgd[2]; }   // :210-211
-}
-// Piece (b): the adjoint of a ray's composite from dC = dL/d color_pred and dA = dL/d alpha_pred, to dgrad and its O-layout copy dhead.
-//     C = sum w rgb (+ (1 - A) bkgd), A = sum w, w_i = a_i T_i, T_i = prod_{j<i} f_j, f_j = (1 - a_j) + 1e-10.  With
-// dL/dw_k = c_k + dA' (c_k = dC . rgb_k, dA' = dA - dC . bkgd):
-//     dL/da_i = T_i (dA' Z_i + (c_i - V_i)),
-//     V_i = sum_{k>i} c_k a_k prod_{i<j<k} f_j   (the colour composited behind sample i, along dC):   V_{i-1} = c_i a_i + f_i V_i,  V_{S-1} = 0
-//     Z_i = 1 - sum_{k>i} a_k prod_{i<j<k} f_j   (what is left of the ray behind sample i):            Z_{i-1} = f_i Z_i - 1e-10,   Z_{S-1} = 1
-// Nothing is divided and the opacity term is never formed as a difference of two sums.  tf.math.cumprod's own gradient
-// (TF 2.4 math_grad.py _CumprodGrad: cumsum(out * grad, reverse) / x) is the same derivative as a quotient by f_i, which on a saturated
-// sample (f_i -> 1e-10) loses the digits the forward product kept, and "dA' (1 - sum)" loses them again when the ray saturates BEHIND
-// sample i (round 5's kernel did both: profiles/r05/soak_train_seed3.txt, case 297).
-// A chunk of 64 samples is a suffix scan of the affine maps X -> b_i + f_i X (composed pairwise), carried from chunk to chunk back to front.
-// A loss on the weights themselves (gw = the ray's row of dL/d w, or NULL): dL/dw_k = c_k + g_k + dA', and everything above holds with
-// c_k + g_k in the place of c_k -- in c_i - V_i and in V_{i-1} = (c_i + g_i) a_i + f_i V_i; dL/d raw rgb = w dC rgb' has no such term.  With
-// gw NULL nothing is added (no + 0.0f): the fused step and a backward without a weight cotangent keep their bits.
-__device__ __forceinline__ void ray_adjoint(const CompositeArgs &a, int ray, int lane, const float *el, const float *T, const float (&dC)[3], float dA, const float *gw) {
-    const int S = a.S;
-    const float *sg = a.sigma + (size_t)ray * S, *ds = a.dists + (size_t)ray * S, *rr = a.raw_rgb + (size_t)ray * S * 3;
-    const float *nz = a.noise ? a.noise + (size_t)ray * S : nullptr;
-    if (a.composite_bkgd) dA -= (dC[0] * a.bkgd[0] + dC[1] * a.bkgd[1]) + dC[2] * a.bkgd[2];
-    float Z_carry = 1.0f, V_carry = 0.0f;                  // Z, V of the last sample of the current chunk (nothing lies behind the ray's end)
-    for (int s0 = ((S - 1) / 64) * 64; s0 >= 0; s0 -= 64) {
-        const int s = s0 + lane;
-        float cs = 0.0f, rgb[3] = {0.0f, 0.0f, 0.0f}, e = 1.0f;
-        float F = 1.0f, Bz = 0.0f, Bv = 0.0f;              // the identity for the lanes past the ray's end
-        if (s < S) {
-            e = el[s];
-            for (int c = 0; c < 3; ++c) rgb[c] = rgb_of(rr[3 * s + c], a.map_exr);
-            cs = (dC[0] * rgb[0] + dC[1] * rgb[1]) + dC[2] * rgb[2];
-            if (gw) cs += gw[s];
-            F = e + 1e-10f; Bz = -1e-10f; Bv = cs * (1.0f - e);
-        }
-        // inclusive suffix composition: lane l ends with the maps of samples l .. 63 of the chunk composed, X_{l-1} = B + F X_63
-        for (int o = 1; o < 64; o <<= 1) {
-            const float Fo = __shfl_down(F, o), Bzo = __shfl_down(Bz, o), Bvo = __shfl_down(Bv, o);
-            if (lane + o < 64) { Bz = fmaf(F, Bzo, Bz); Bv = fmaf(F, Bvo, Bv); F *= Fo; }
-        }
-        float Fn = __shfl_down(F, 1), Bzn = __shfl_down(Bz, 1), Bvn = __shfl_down(Bv, 1);   // the lanes strictly behind this one
-        if (lane == 63) { Fn = 1.0f; Bzn = 0.0f; Bvn = 0.0f; }
-        const float Z = fmaf(Fn, Z_carry, Bzn), V = fmaf(Fn, V_carry, Bvn);
-        if (s < S) {
-            const float w = (1.0f - e) * T[s];
-            const float d_a = T[s] * fmaf(dA, Z, cs - V);
-            const float sig = nz ? sg[s] + nz[s] : sg[s];
-            float gr[4];
-            for (int c = 0; c < 3; ++c) {
-                const float raw = rr[3 * s + c];
-                const float drgb = a.map_exr ? (raw > 0.0f ? 1.0f : expf(raw)) : rgb[c] * (1.0f - rgb[c]);
-                gr[c] = w * dC[c] * drgb;
-            }
-            gr[3] = sig > 0.0f ? d_a * ds[s] * e : 0.0f;                                       // da/dsigma = dist exp(-sigma dist)
-            const long long m = (long long)ray * S + s;
-            *reinterpret_cast<f32x4 *>(a.dgrad + 4 * m) = f32x4{gr[0], gr[1], gr[2], gr[3]};
-            for (int r = 0; r < 4; ++r) a.dhead[dhead_at(m, r)] = gr[r];
-        }
-        const float F0 = __shfl(F, 0);
-        Z_carry = fmaf(F0, Z_carry, __shfl(Bz, 0)); V_carry = fmaf(F0, V_carry, __shfl(Bv, 0));
-    }
-}
-// the fused step's composite: (a), the ray's terms of the loss and their derivatives (loss.py:6-49), (b)
+// the fused step's composite: the forward, the ray's terms of the loss and their derivatives (loss.py:6-49: both losses are means over the
+// rays, so a ray's gradient needs nothing of the others), the adjoint
 __global__ __launch_bounds__(256) void composite_loss_kernel(CompositeArgs a) {
     __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    fetch_args(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0) zero_dhead_tail(a);
     const int ray = blockIdx.x * 4 + wave;
     if (ray >= a.n_rays) return;
     float *el = sh_a[wave], *T = sh_T[wave];
-    ray_transmittance(a, ray, lane, el, T);
-    float c0, c1, c2, A;
-    ray_composite(a, ray, lane, el, T, c0, c1, c2, A);
-    const float cp[3] = {c0, c1, c2};
+    const WholeRay v(a, ray);
+    float cp[3], A;
+    ray_forward(v, a, lane, el, T, cp, A);
     float dC[3], dA = 0.0f, total = 0.0f;
     {
         const float inv_c = 1.0f / (float)(a.n_rays * 3), inv_a = 1.0f / (float)a.n_rays;
         float mask = 1.0f;
         if (a.kind == NTX_LOSS_ALPHA && a.filter_color_loss) mask = a.use_hard_mask ? (a.alpha_true[ray] > 0.0f ? 1.0f : 0.0f) : a.alpha_true[ray];   // :29-35
         for (int c = 0; c < 3; ++c) {
-            float v, gr;
-            loss_term(a.loss_fn, a.color_true[3 * ray + c] * mask, cp[c] * mask, inv_c, v, gr);
-            total += v; dC[c] = gr * mask;
+            float val, gr;
+            loss_term(a.loss_fn, a.color_true[3 * ray + c] * mask, cp[c] * mask, inv_c, val, gr);
+            total += val; dC[c] = gr * mask;
         }
-        if (a.kind == NTX_LOSS_ALPHA) { float v; loss_term(a.alpha_loss_fn, a.alpha_true[ray], A, inv_a, v, dA); total += a.gamma * v; dA *= a.gamma; }   // :38
+        if (a.kind == NTX_LOSS_ALPHA) { float val; loss_term(a.alpha_loss_fn, a.alpha_true[ray], A, inv_a, val, dA); total += a.gamma * val; dA *= a.gamma; }   // :38
     }
-    if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; a.ray_loss[ray] = total; }
-    ray_adjoint(a, ray, lane, el, T, dC, dA, nullptr);
+    store_prediction(a, ray, lane, cp, A);
+    if (lane == 0) a.ray_loss[ray] = total;
+    ray_adjoint(v, a, lane, el, T, dC, dA, nullptr);
 }
-// ntx_train_forward's composite: (a) alone -- the predictions (and the weights a coarse pass hands on); nothing of the loss, no gradient
+// ntx_train_forward's composite: the forward alone -- the predictions (and the weights a coarse pass hands on); nothing of the loss, no gradient
 __global__ __launch_bounds__(256) void composite_forward_kernel(CompositeArgs a) {
     __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    fetch_args(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ray = blockIdx.x * 4 + wave;
     if (ray >= a.n_rays) return;
-    float *el = sh_a[wave], *T = sh_T[wave];
-    ray_transmittance(a, ray, lane, el, T);
-    float c0, c1, c2, A;
-    ray_composite(a, ray, lane, el, T, c0, c1, c2, A);
-    if (lane == 0) { a.color[3 * ray] = c0; a.color[3 * ray + 1] = c1; a.color[3 * ray + 2] = c2; a.alpha[ray] = A; }
+    float c[3], A;
+    ray_forward(WholeRay(a, ray), a, lane, sh_a[wave], sh_T[wave], c, A);
+    store_prediction(a, ray, lane, c, A);
 }
-// ntx_train_backward's composite: el and T again from what the pending forward left (sigma, dists, noise, raw_rgb), then (b) from the
+// ntx_train_backward's composite: el and T again from what the pending forward left (sigma, dists, noise, raw_rgb), then the adjoint from the
 // caller's cotangents d_color [N][3] and d_alpha [N] (NULL: 0).  A ray whose depths are not finite has dists 0 throughout: it composites to
-// nothing, and its gradient is 0 whatever its cotangent holds (inf and NaN included) -- by selecting a zero cotangent for it, so that (b)
-// runs on the same numbers as with the cotangent zeroed by the caller, never by a product with what may not be finite.  d_weights: NULL, or
-// [N][S] = dL/d weights (ntx_trainer_weight_cotangent); such a ray selects none of it either.
+// nothing, and its gradient is 0 whatever its cotangent holds (inf and NaN included) -- by selecting a zero cotangent for it, so that the
+// adjoint runs on the same numbers as with the cotangent zeroed by the caller, never by a product with what may not be finite.  d_weights:
+// NULL, or [N][S] = dL/d weights (ntx_trainer_weight_cotangent); such a ray selects none of it either.
 __global__ __launch_bounds__(256) void composite_adjoint_kernel(CompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha,
                                                                 const float *__restrict__ d_weights) {
     __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    fetch_args(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0) zero_dhead_tail(a);
     const int ray = blockIdx.x * 4 + wave;
     if (ray >= a.n_rays) return;
     float *el = sh_a[wave], *T = sh_T[wave];
-    ray_transmittance(a, ray, lane, el, T);
-    const float *ds = a.dists + (size_t)ray * a.S;
+    const WholeRay v(a, ray);
+    (void)ray_transmittance(v, lane, el, T);
     bool live = false;
-    for (int s = lane; s < a.S; s += 64) live = live || ds[s] != 0.0f;
+    for (int s = lane; s < a.S; s += 64) live = live || v.ds[s] != 0.0f;
     live = __any(live) != 0;
     float dC[3];
     for (int c = 0; c < 3; ++c) dC[c] = live ? d_color[3 * ray + c] : 0.0f;
     const float dA = live && d_alpha ? d_alpha[ray] : 0.0f;
-    ray_adjoint(a, ray, lane, el, T, dC, dA, live && d_weights ? d_weights + (size_t)ray * a.S : nullptr);
+    ray_adjoint(v, a, lane, el, T, dC, dA, live ? d_weights : nullptr);
+}
+// ntx_train_forward_instanced's composite, the network's raw outputs in compact rows.  A ray with hit == 0 is 0 / 0 and its weights are 0.
+__global__ __launch_bounds__(256) void inst_composite_forward_kernel(InstCompositeArgs a) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    fetch_args(a);
+    const StepSamples &p = a.s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long ray = (long long)blockIdx.x * 4 + wave;
+    if (ray >= p.n_rays) return;
+    float c[3] = {0.0f, 0.0f, 0.0f}, A = 0.0f;
+    if (!p.hit[ray]) { if (a.weights) for (int s = lane; s < p.S; s += 64) a.weights[ray * p.S + s] = 0.0f; }
+    else ray_forward(InstancedRay(a, ray), a, lane, sh_a[wave], sh_T[wave], c, A);
+    store_prediction(a, ray, lane, c, A);
+}
+// Its adjoint from the caller's cotangents, to dgrad[row] of the live samples.  A ray with hit == 0 has no live sample: nothing of it is
+// written whatever its cotangent holds, which is not even read.  d_weights: NULL, or [N][S] = dL/d weights of the S samples.
+__global__ __launch_bounds__(256) void inst_composite_adjoint_kernel(InstCompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha,
+                                                                     const float *__restrict__ d_weights) {
+    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
+    fetch_args(a);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long ray = (long long)blockIdx.x * 4 + wave;
+    if (ray >= a.s.n_rays || !a.s.hit[ray]) return;
+    float *el = sh_a[wave], *T = sh_T[wave];
+    const InstancedRay v(a, ray);
+    (void)ray_transmittance(v, lane, el, T);
+    const float dC[3] = {d_color[3 * ray], d_color[3 * ray + 1], d_color[3 * ray + 2]};
+    ray_adjoint(v, a, lane, el, T, dC, d_alpha ? d_alpha[ray] : 0.0f, d_weights);
 }
 // ---------------------------------------------------------------------------------------------------------------------------
 // The instanced step (ntx_train_forward_instanced): InstanceRenderer.evaluate_model + map_model_output (renderer.py:247-354) with the
@@ -284,140 +201,6 @@ __global__ __launch_bounds__(256) void live_rows_kernel(const float *__restrict_
         if (s < S) row_of[m] = lv ? row : -1;
         if (lv) live[row] = (int)m;
         base += __popcll(b);
-    }
-}
-// The instanced composite (renderer.py:318-354): the network's raw outputs in compact rows (sigma [n_live], raw_rgb [n_live][3]), everything else
-// in the caller's [N][S] buffers.  A live sample: sigma' = sigma * alpha_weight * density_scale (:300), a = 1 - exp(-relu(sigma') dists /
-// patch_scale) (:339).  A sample that is not live has a = 0 exactly, its factor of the running product is 1 + 1e-10.  One appended sample
-// (color_last as is, alpha_last as an alpha) closes the ray (:331, :339).  A ray with hit == 0 is 0 / 0, also under the background (:313-314).
-struct InstCompositeArgs {
-    StepSamples s; const float *raw_rgb, *sigma;
-    int map_exr, composite_bkgd; float bkgd[3];
-    float *color, *alpha;                      // [N][3], [N]
-    float *weights;                            // NULL, or [N][S]: the forward's weights a_s T_s of the S samples (0 where a sample is not live, and on a ray with hit == 0)
-    float *dgrad;                              // [n_live][4] in compact row order
-};
-// ray_transmittance for such a ray: el[s] = exp(-relu(sigma') dists / patch_scale), 1 where the sample is not live, and T[s]; the factors in
-// the same el + 1e-10 form (see there).  Returns the product of all S factors: the transmittance in front of the appended sample.
-__device__ __forceinline__ float inst_transmittance(const InstCompositeArgs &a, long long ray, int lane, float *el, float *T) {
-    const StepSamples &p = a.s;
-    const int S = p.S;
-    for (int s = lane; s < S; s += 64) {
-        const long long m = ray * S + s;
-        const int row = p.row_of[m];
-        float e = 1.0f;
-        if (row >= 0) {
-            const float v = a.sigma[row] * (p.alpha_weight ? p.alpha_weight[m] : 1.0f) * p.density_scale;
-            const float r = v > 0.0f ? v : 0.0f;
-            e = expf(-r * p.dists[m] / p.patch_scale);
-        }
-        el[s] = e;
-    }
-    __builtin_amdgcn_wave_barrier();
-    float carry = 1.0f;
-    for (int s0 = 0; s0 < S; s0 += 64) {
-        const int s = s0 + lane;
-        float f = s < S ? el[s] + 1e-10f : 1.0f, incl = f;
-        for (int o = 1; o < 64; o <<= 1) { const float w = __shfl_up(incl, o); if (lane >= o) incl *= w; }
-        float excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = 1.0f;
-        if (s < S) T[s] = carry * excl;
-        carry *= __shfl(incl, 63);
-    }
-    __builtin_amdgcn_wave_barrier();
-    return carry;
-}
-__global__ __launch_bounds__(256) void inst_composite_forward_kernel(InstCompositeArgs a) {
-    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
-    const StepSamples &p = a.s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long ray = (long long)blockIdx.x * 4 + wave;
-    if (ray >= p.n_rays) return;
-    if (!p.hit[ray]) {
-        if (lane < 3) a.color[3 * ray + lane] = 0.0f;
-        if (lane == 3) a.alpha[ray] = 0.0f;
-        if (a.weights) for (int s = lane; s < p.S; s += 64) a.weights[ray * p.S + s] = 0.0f;
-        return;
-    }
-    float *el = sh_a[wave], *T = sh_T[wave];
-    const float T_last = inst_transmittance(a, ray, lane, el, T);
-    float c[3] = {0.0f, 0.0f, 0.0f}, A = 0.0f;
-    for (int s = lane; s < p.S; s += 64) {
-        const int row = p.row_of[ray * p.S + s];
-        if (row < 0) { if (a.weights) a.weights[ray * p.S + s] = 0.0f; continue; }             // a = 0: no weight
-        const float w = (1.0f - el[s]) * T[s];
-        for (int k = 0; k < 3; ++k) c[k] += w * rgb_of(a.raw_rgb[3 * (size_t)row + k], a.map_exr);
-        A += w;
-        if (a.weights) a.weights[ray * p.S + s] = w;                                            // (the appended sample's is alpha_pred - sum_s w_s)
-    }
-    const float wl = p.alpha_last[ray] * T_last;                                                // the appended sample
-    A = wave_sumf(A) + wl;
-    for (int k = 0; k < 3; ++k) {
-        c[k] = wave_sumf(c[k]) + wl * p.color_last[3 * ray + k];
-        if (a.composite_bkgd) c[k] += (1.0f - A) * a.bkgd[k];                                   // :351-352
-    }
-    if (lane < 3) a.color[3 * ray + lane] = lane == 0 ? c[0] : lane == 1 ? c[1] : c[2];
-    if (lane == 3) a.alpha[ray] = A;
-}
-// Its adjoint from the caller's cotangents: ray_adjoint's recurrences (see there) with the appended sample behind sample S - 1, so the
-// carries start at V_{S-1} = (dC . color_last) alpha_last and Z_{S-1} = ((1 - alpha_last) + 1e-10) - 1e-10 instead of 0 and 1.  A sample
-// that is not live is the map X -> -1e-10 + (1 + 1e-10) X for Z and the identity's for V, and writes nothing.  dL/d sigma of a live sample:
-// d_a (dists / patch_scale) e alpha_weight density_scale where sigma' > 0.  A ray with hit == 0 has no live sample: nothing of it is
-// written whatever its cotangent holds, which is not even read.  d_weights: NULL, or [N][S] = dL/d weights of the S samples, read at live
-// samples only and added to c_k as in ray_adjoint (the appended sample has no stored weight and takes none).
-__global__ __launch_bounds__(256) void inst_composite_adjoint_kernel(InstCompositeArgs a, const float *__restrict__ d_color, const float *__restrict__ d_alpha,
-                                                                     const float *__restrict__ d_weights) {
-    __shared__ float sh_a[4][MAX_TRAIN_SAMPLES], sh_T[4][MAX_TRAIN_SAMPLES];
-    const StepSamples &p = a.s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, S = p.S;
-    const long long ray = (long long)blockIdx.x * 4 + wave;
-    if (ray >= p.n_rays || !p.hit[ray]) return;
-    float *el = sh_a[wave], *T = sh_T[wave];
-    (void)inst_transmittance(a, ray, lane, el, T);
-    const float dC[3] = {d_color[3 * ray], d_color[3 * ray + 1], d_color[3 * ray + 2]};
-    float dA = d_alpha ? d_alpha[ray] : 0.0f;
-    if (a.composite_bkgd) dA -= (dC[0] * a.bkgd[0] + dC[1] * a.bkgd[1]) + dC[2] * a.bkgd[2];
-    const float al = p.alpha_last[ray];
-    float V_carry = ((dC[0] * p.color_last[3 * ray] + dC[1] * p.color_last[3 * ray + 1]) + dC[2] * p.color_last[3 * ray + 2]) * al;
-    float Z_carry = ((1.0f - al) + 1e-10f) - 1e-10f;
-    for (int s0 = ((S - 1) / 64) * 64; s0 >= 0; s0 -= 64) {
-        const int s = s0 + lane;
-        const long long m = ray * S + s;
-        const int row = s < S ? p.row_of[m] : -1;
-        float cs = 0.0f, rgb[3] = {0.0f, 0.0f, 0.0f}, e = 1.0f;
-        float F = 1.0f, Bz = 0.0f, Bv = 0.0f;              // the identity for the lanes past the ray's end
-        if (s < S) {
-            e = el[s];
-            if (row >= 0) {
-                for (int c = 0; c < 3; ++c) rgb[c] = rgb_of(a.raw_rgb[3 * (size_t)row + c], a.map_exr);
-                cs = (dC[0] * rgb[0] + dC[1] * rgb[1]) + dC[2] * rgb[2];
-                if (d_weights) cs += d_weights[m];
-            }
-            F = e + 1e-10f; Bz = -1e-10f; Bv = row >= 0 ? cs * (1.0f - e) : 0.0f;
-        }
-        for (int o = 1; o < 64; o <<= 1) {
-            const float Fo = __shfl_down(F, o), Bzo = __shfl_down(Bz, o), Bvo = __shfl_down(Bv, o);
-            if (lane + o < 64) { Bz = fmaf(F, Bzo, Bz); Bv = fmaf(F, Bvo, Bv); F *= Fo; }
-        }
-        float Fn = __shfl_down(F, 1), Bzn = __shfl_down(Bz, 1), Bvn = __shfl_down(Bv, 1);   // the lanes strictly behind this one
-        if (lane == 63) { Fn = 1.0f; Bzn = 0.0f; Bvn = 0.0f; }
-        const float Z = fmaf(Fn, Z_carry, Bzn), V = fmaf(Fn, V_carry, Bvn);
-        if (row >= 0) {
-            const float w = (1.0f - e) * T[s];
-            const float d_a = T[s] * fmaf(dA, Z, cs - V);
-            const float aw = p.alpha_weight ? p.alpha_weight[m] : 1.0f;
-            const float sig = a.sigma[row] * aw * p.density_scale;
-            float gr[4];
-            for (int c = 0; c < 3; ++c) {
-                const float raw = a.raw_rgb[3 * (size_t)row + c];
-                const float drgb = a.map_exr ? (raw > 0.0f ? 1.0f : expf(raw)) : rgb[c] * (1.0f - rgb[c]);
-                gr[c] = w * dC[c] * drgb;
-            }
-            gr[3] = sig > 0.0f ? d_a * (p.dists[m] / p.patch_scale) * e * aw * p.density_scale : 0.0f;
-            *reinterpret_cast<f32x4 *>(a.dgrad + 4 * (size_t)row) = f32x4{gr[0], gr[1], gr[2], gr[3]};
-        }
-        const float F0 = __shfl(F, 0);
-        Z_carry = fmaf(F0, Z_carry, __shfl(Bz, 0)); V_carry = fmaf(F0, V_carry, __shfl(Bv, 0));
     }
 }
 // the loss: the rays' terms added up by one workgroup in a fixed order
@@ -619,13 +402,24 @@ static int step_network(ntx_trainer *t, const float *rays_o, const float *rays_d
     *rays = StepRays{rays_o, rays_d, z, params, cone_scale, rays_per_param_row, n_rays, S, blur_idx, d.n_geo, d.n_app, d.pos_freq, d.dir_freq, d.param_freq};
     return t->backend->forward(*rays, (hipStream_t)stream);
 }
+// what both composites' arguments share: the raw outputs, the flags' options, the background (default 1), the predictions (default: the
+// handle's buffers), the registered weights (ntx_trainer_composite_weights: a forward's; the backwards set NULL) and dgrad
+static void composite_common(const ntx_trainer *t, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred, CompositeCommon *c) {
+    c->raw_rgb = t->raw_rgb; c->sigma = t->sigma; c->map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0; c->composite_bkgd = (flags & NTX_FLAG_COMPOSITE_BKGD) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) c->bkgd[k] = bkgd ? bkgd[k] : 1.0f;
+    c->color = color_pred ? color_pred : t->color; c->alpha = alpha_pred ? alpha_pred : t->alpha_out; c->weights = t->weights_out; c->dgrad = t->dgrad;
+}
+// what a step left for the gradient getters, under the modes that are on: a plain step's parameter rows and rays (smp_rays = 0), or an
+// instanced step's rays x S of per-sample gradients (rows = rays = 0) -- each kind of getter refuses the other kind's step
+static void step_left(ntx_trainer *t, long long rows, long long rays, long long smp_rays, int smp_S) {
+    if (t->pg_mode != 0) { t->pg_rows = rows; t->spg_rays = smp_rays; t->spg_S = smp_S; }
+    if (t->ig_mode != 0) { t->ig_rays = rays; t->ig_smp_rays = smp_rays; t->ig_S = smp_S; }
+}
+static void plain_step_left(ntx_trainer *t, const StepRays &rays) { step_left(t, (rays.n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row, rays.n_rays, 0, 0); }
 static CompositeArgs composite_args(const ntx_trainer *t, const StepRays &rays, const float *noise, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred) {
     CompositeArgs c{};
-    c.raw_rgb = t->raw_rgb; c.sigma = t->sigma; c.dists = t->dists; c.noise = noise; c.n_rays = (int)rays.n_rays; c.S = rays.S; c.map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0;
-    c.composite_bkgd = (flags & NTX_FLAG_COMPOSITE_BKGD) ? 1 : 0;
-    for (int k = 0; k < 3; ++k) c.bkgd[k] = bkgd ? bkgd[k] : 1.0f;
-    c.weights = t->weights_out;
-    c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.ray_loss = t->ray_loss; c.dgrad = t->dgrad; c.dhead = t->dhead; c.M = rays.M();
+    composite_common(t, flags, bkgd, color_pred, alpha_pred, &c);
+    c.dists = t->dists; c.noise = noise; c.n_rays = (int)rays.n_rays; c.S = rays.S; c.ray_loss = t->ray_loss; c.dhead = t->dhead; c.M = rays.M();
     return c;
 }
 
@@ -633,9 +427,8 @@ static CompositeArgs composite_args(const ntx_trainer *t, const StepRays &rays, 
 // under ntx_trainer_enable_param_gradients -- the per-sample dL/d params (placed at the first such step, for the capacity)
 static InstCompositeArgs inst_composite_args(const ntx_trainer *t, const StepSamples &s, uint32_t flags, const float *bkgd, float *color_pred, float *alpha_pred) {
     InstCompositeArgs c{};
-    c.s = s; c.raw_rgb = t->raw_rgb; c.sigma = t->sigma; c.map_exr = (flags & NTX_FLAG_MAP_EXR) ? 1 : 0; c.composite_bkgd = (flags & NTX_FLAG_COMPOSITE_BKGD) ? 1 : 0;
-    for (int k = 0; k < 3; ++k) c.bkgd[k] = bkgd ? bkgd[k] : 1.0f;
-    c.color = color_pred ? color_pred : t->color; c.alpha = alpha_pred ? alpha_pred : t->alpha_out; c.dgrad = t->dgrad;
+    composite_common(t, flags, bkgd, color_pred, alpha_pred, &c);
+    c.s = s;
     return c;
 }
 static int backward_instanced(ntx_trainer *t, const float *d_color, const float *d_alpha, const float *d_weights, hipStream_t st) {
@@ -645,13 +438,13 @@ static int backward_instanced(ntx_trainer *t, const float *d_color, const float 
         t->mem.alloc(&t->d_pts, (size_t)t->cap * 3); t->mem.alloc(&t->d_dirs, (size_t)t->cap * 3);
         if (t->mem.rc != NTX_OK) return t->mem.rc;
     }
-    const InstCompositeArgs c = inst_composite_args(t, s, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
+    InstCompositeArgs c = inst_composite_args(t, s, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
+    c.weights = nullptr;                                                                        // the adjoint alone: nothing of the forward is written again
     if (s.n_live > 0) hipLaunchKernelGGL(inst_composite_adjoint_kernel, dim3((unsigned)((s.n_rays + 3) / 4)), dim3(256), 0, st, c, d_color, d_alpha, d_weights);
     int rc = t->backend->backward_samples(s, t->sample_pg, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
-    if (t->pg_mode != 0) { t->spg_rays = s.n_rays; t->spg_S = s.S; t->pg_rows = 0; }
-    if (t->ig_mode != 0) { t->ig_smp_rays = s.n_rays; t->ig_S = s.S; t->ig_rays = 0; }
+    step_left(t, 0, 0, s.n_rays, s.S);
     return NTX_OK;
 }
 
@@ -681,8 +474,7 @@ int ntx_train_step_gradients(ntx_trainer *t, const float *rays_o, const float *r
     rc = t->backend->backward(rays, st);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
-    if (t->pg_mode != 0) { t->pg_rows = (n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row; t->spg_rays = 0; }
-    if (t->ig_mode != 0) { t->ig_rays = n_rays; t->ig_smp_rays = 0; }
+    plain_step_left(t, rays);
     return NTX_OK;
 }
 
@@ -716,14 +508,13 @@ int ntx_train_backward(ntx_trainer *t, const float *d_color, const float *d_alph
     if (t->pending.samples) return backward_instanced(t, d_color, d_alpha, d_weights, (hipStream_t)stream);
     const StepRays &rays = t->pending.rays;
     CompositeArgs c = composite_args(t, rays, t->pending.noise, t->pending.flags, t->pending.bkgd, nullptr, nullptr);
-    c.weights = nullptr;                                                                        // (b) alone: nothing of the forward is written again
+    c.weights = nullptr;                                                                        // the adjoint alone: nothing of the forward is written again
     t->step_noise = t->pending.noise;
     hipLaunchKernelGGL(composite_adjoint_kernel, dim3((unsigned)((rays.n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c, d_color, d_alpha, d_weights);
     int rc = t->backend->backward(rays, (hipStream_t)stream);
     if (rc != NTX_OK) return rc;
     TRAIN_TRY(hipGetLastError());
-    if (t->pg_mode != 0) { t->pg_rows = (rays.n_rays + rays.rays_per_param_row - 1) / rays.rays_per_param_row; t->spg_rays = 0; }
-    if (t->ig_mode != 0) { t->ig_rays = rays.n_rays; t->ig_smp_rays = 0; }
+    plain_step_left(t, rays);
     return NTX_OK;
 }
 
@@ -758,8 +549,7 @@ int ntx_train_forward_instanced(ntx_trainer *t, const float *rays_d_map, const f
                   d.dir_freq, d.param_freq, patch_scale, density_scale, t->live, t->row_of, n_live};
     int rc = t->backend->forward_samples(s, st);
     if (rc != NTX_OK) return rc;
-    InstCompositeArgs c = inst_composite_args(t, s, flags, bkgd, color_pred, alpha_pred);
-    c.weights = t->weights_out;                                                                 // ntx_trainer_composite_weights: [N][S], the forward alone writes them
+    const InstCompositeArgs c = inst_composite_args(t, s, flags, bkgd, color_pred, alpha_pred);
     hipLaunchKernelGGL(inst_composite_forward_kernel, dim3(ray_grid), dim3(256), 0, st, c);
     TRAIN_TRY(hipGetLastError());
     t->pending.smp = s; t->pending.flags = flags; t->pending.noise = nullptr; t->pending.samples = true;
