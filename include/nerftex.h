@@ -171,8 +171,18 @@ typedef struct ntx_render_opts {
  *                        ~2^-22 relative per product: 2.8e-6 from the float32 kernel on the bench image, ~2.8x faster.  Not
  *                        bit-identical to NTX_PRECISION_F32.  Range: |activation| and |weight| <= 65504, beyond that the
  *                        sample becomes inf/NaN (reported through NTX_FLAG_CHECK_NUMERICS).  Every family and all three
- *                        entry points. */
-typedef enum ntx_precision { NTX_PRECISION_F32 = 0, NTX_PRECISION_FP16X3 = 1 } ntx_precision;
+ *                        entry points.
+ *   NTX_PRECISION_BF16X6 opt-in, TRAINING only (ntx_trainer_set_precision below; no render entry takes it): the contractions of the
+ *                        layer-by-layer training step with both operands split as v = v0 + v1 + v2, v0 = bf16(v), v1 = bf16(v - v0),
+ *                        v2 = bf16(v - v0 - v1) (round to nearest even, the subtractions in float32) and the six products of order
+ *                        <= 2 -- a0b2, a1b1, a2b0, a0b1, a1b0, then a0b0 -- taken on the 16-bit matrix cores
+ *                        (v_mfma_f32_32x32x16_bf16) into float32, smallest first.  The three terms carry 24 mantissa bits and bf16
+ *                        has float32's exponent range, so the result is at or below float32's own rounding error at every scale of
+ *                        the operands (the cotangents of a mean loss, 1e-6 .. 1e-9 a sample, included -- which is why fp16x3 cannot
+ *                        train): no loss scaling, no amax pass.  Operands, weights, Adam and every other kernel stay float32.  Not
+ *                        bit-identical to NTX_PRECISION_F32.  An Inf operand may come out as NaN in its row (inf - inf in the
+ *                        split); a finite |v| beyond bf16's largest finite value (3.39e38) turns Inf. */
+typedef enum ntx_precision { NTX_PRECISION_F32 = 0, NTX_PRECISION_FP16X3 = 1, NTX_PRECISION_BF16X6 = 2 } ntx_precision;
 /* The precision is chosen PER CALL with NTX_FLAG_FP16X3 in `flags`; a context holds both weight images and no mutable
  * precision state, so two callers may share a context on different precisions. */
 
@@ -862,6 +872,27 @@ int ntx_trainer_weight_cotangent(ntx_trainer *t, const float *d_weights_dev);
  * ntx_instancer_model_input does for it is to remember its stream. */
 int ntx_instancer_sample_uv(ntx_instancer *inst, const float *rays_o, const float *rays_d, const float *t, const float *dists, int64_t n_rays,
                             int n_pts, float step_size, float *uv_out /* [N,S,2] */, uint8_t *found_out /* [N,S] */);
+
+/* Opt-in bf16x6 training (ABI v7, appended): the precision of the contractions of a LAYER-BY-LAYER trainer (ntx_trainer_create_flex,
+ * ntx_trainer_create_flex_ex) -- trunk and branch layers forward, dX, dW and db, and the terms behind dL/d params and dL/d inputs, of plain
+ * and instanced steps -- NTX_PRECISION_F32 (the default) or NTX_PRECISION_BF16X6 (the arithmetic: beside the enum above).  The heads, the
+ * encoder, the composite, the reductions, Adam and the weights are float32 either way, so checkpoints, gradients and all getters keep their
+ * meaning.  It takes effect from the next step and can be changed back: a float32 step behind a bf16x6 one is bit for bit the step of a
+ * trainer that never left float32.  NTX_E_INVALID: t NULL, a value that is no ntx_precision, or a forward pending its ntx_train_backward.
+ * NTX_E_UNSUPPORTED: NTX_PRECISION_FP16X3 (a half cannot hold the cotangents), a chain handle (ntx_trainer_create; an IPE trainer is one).
+ * A refused call changes nothing. */
+int ntx_trainer_set_precision(ntx_trainer *t, int precision);
+/* The handle's current precision (an ntx_precision), -1 for NULL. */
+int ntx_trainer_precision(const ntx_trainer *t);
+/* ntx_gemm_f32_ex's contraction through the bf16x6 body, for tests and benches of the kernel itself: the same arguments with the same
+ * meaning -- both A forms, bias, relu, mask, accumulate, the K split, colsum (the float32 column sums of B, bit-equal to ntx_gemm_f32_ex's)
+ * -- and the same NTX_E_INVALID refusals, all before the first launch, so a refused call has written nothing.  Operands and results are
+ * float32 in memory.  THE STREAM.  This entry takes no `ntx_stream` and launches on the null stream: every prototype with an ntx_stream
+ * parameter must be registered in the stream-order tests' tables (tests/stream_common.py), and this entry came with a change that adds test
+ * files only.  A stream-taking variant is an appended entry (_ex2), not a change of this one; the training step itself runs the body on the
+ * step's stream. */
+int ntx_gemm_bf16x6_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
+                       const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum);
 
 #ifdef __cplusplus
 }

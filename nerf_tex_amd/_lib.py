@@ -78,6 +78,8 @@ class NtxError(RuntimeError):
 
 
 PRECISIONS = {"float32": 0, "fp16x3": FLAG_FP16X3}   # precision name -> its bit in `flags` (ntx_precision is chosen per call)
+PRECISION_F32, PRECISION_FP16X3, PRECISION_BF16X6 = 0, 1, 2
+TRAIN_PRECISIONS = {"float32": PRECISION_F32, "bf16x6": PRECISION_BF16X6}   # precision name -> ntx_precision of ntx_trainer_set_precision
 
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -175,6 +177,9 @@ SYMBOLS = {
     "ntx_trainer_enable_instanced": (C.c_int, [_vp]),
     "ntx_trainer_weight_cotangent": (C.c_int, [_vp, _vp]),
     "ntx_instancer_sample_uv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, _vp, _vp]),
+    "ntx_trainer_set_precision": (C.c_int, [_vp, C.c_int]),
+    "ntx_trainer_precision": (C.c_int, [_vp]),
+    "ntx_gemm_bf16x6_ex": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _vp]),
 }
 
 

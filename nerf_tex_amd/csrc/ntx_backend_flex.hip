@@ -568,7 +568,7 @@ void FlexBackend::branch_forward(const FlexBranch &b, const FlexDst *dst, int n_
     const float *W = t->w;
     for (const FlexLayer &l : b.layers) {
         GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = W + l.w; g.ldb = l.out; g.C = l.Y; g.ldc = l.ldy; g.M = (int)M; g.N = l.out; g.K = l.in; g.bias = W + l.b; g.relu = 1;
-        launch_gemm(st, true, g);
+        g.precision = t->precision; launch_gemm(st, true, g);
     }
     const FlexLayer &last = b.layers.back();
     FlexBranchCopyArgs c{}; c.src = last.Y; c.lds = last.ldy; c.width = pw; c.off = b.off; c.n_dst = n_dst; c.M = M;
@@ -612,7 +612,7 @@ void FlexBackend::network_forward(long long M, hipStream_t st) {
         const FlexLayer &l = layers[i];
         if ((int)i == t->desc.depth + 1 && app.exists()) branch_forward(app, &dir_dst, 1, M, st);      // :96-101: in front of the first layer that reads dir_map
         GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = W + l.w; g.ldb = l.out; g.C = l.Y; g.ldc = l.ldy; g.M = (int)M; g.N = l.out; g.K = l.in; g.bias = W + l.b; g.relu = l.relu;
-        launch_gemm(st, true, g);
+        g.precision = t->precision; launch_gemm(st, true, g);
     }
     const unsigned head_grid = (unsigned)std::min<long long>((M + 3) / 4, (long long)t->cus * 8);
     const FlexLayer &lt = layers[last_trunk], &lh = layers[half];
@@ -635,20 +635,20 @@ void FlexBackend::branch_term(FlexBranch &b, const FlexLayer &consumer, const fl
     const FlexLayer &last = b.layers.back();
     GemmArgs g{}; g.A = dY; g.lda = ldg; g.B = wt + consumer.bwt; g.ldb = pw; g.C = BG[0]; g.ldc = ldb; g.M = (int)M; g.N = pw; g.K = consumer.out;
     g.accumulate = b.consumers_met++ > 0; g.mask = last.Y; g.ldmask = last.ldy;
-    launch_gemm(st, true, g);
+    g.precision = t->precision; launch_gemm(st, true, g);
 }
 // A reader's term of the gradient at a group's parameter features (0 geometry, 1 appearance): PG (+)= dY . W[feature rows]^T, the readers in
 // the order the way back meets them
 void FlexBackend::param_term(int group, long long pwt, int n_in, const float *dY, int lddy, int K, long long M, hipStream_t st) {
     GemmArgs g{}; g.A = dY; g.lda = lddy; g.B = wt + pwt; g.ldb = n_in; g.C = PG[group]; g.ldc = ldpg[group]; g.M = (int)M; g.N = n_in; g.K = K;
     g.accumulate = pg_met[group]++ > 0;
-    launch_gemm(st, true, g);
+    g.precision = t->precision; launch_gemm(st, true, g);
 }
 // A reader's term of the gradient at the FF(xyz) rows (group 0) or the FF(dir) rows (1): IG (+)= dY . W[first K3 rows]^T, in the same order
 void FlexBackend::input_term(int group, const FlexLayer &l, const float *dY, long long M, hipStream_t st) {
     GemmArgs g{}; g.A = dY; g.lda = ldg; g.B = wt + l.xwt; g.ldb = K3[group]; g.C = IG[group]; g.ldc = ldig[group]; g.M = (int)M; g.N = K3[group]; g.K = l.out;
     g.accumulate = ig_met[group]++ > 0;
-    launch_gemm(st, true, g);
+    g.precision = t->precision; launch_gemm(st, true, g);
 }
 // ... and from there through the branch, as through the trunk: dW / db per layer over ranges of FLEX_SPLIT samples, dX masked by the layer in
 // front; nothing behind the first layer (the inputs are not trained)
@@ -660,7 +660,7 @@ void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split,
         if (t->takes_weight_gradients()) {
             GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldb; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
             g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
-            launch_gemm(st, false, g, n_split);
+            g.precision = t->precision; launch_gemm(st, false, g, n_split);
             reduce(st, n_split, partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
         }
         if (j == 0) {                                                        // behind the first layer lie the parameter features: dY_0 . W_0^T where dL/d params is asked for
@@ -670,7 +670,7 @@ void FlexBackend::branch_backward(const FlexBranch &b, long long M, int n_split,
         const FlexLayer &s = b.layers[j - 1];
         GemmArgs x{}; x.A = dY; x.lda = ldb; x.B = wt + l.wt; x.ldb = l.in; x.C = BG[cur ^ 1]; x.ldc = ldb; x.M = (int)M; x.N = l.in; x.K = l.out;
         x.mask = s.Y; x.ldmask = s.ldy;
-        launch_gemm(st, true, x);
+        x.precision = t->precision; launch_gemm(st, true, x);
         cur ^= 1;
     }
 }
@@ -716,7 +716,7 @@ void FlexBackend::network_backward(long long M, hipStream_t st) {
         if (wgrad) {   // dW_i and db_i
             GemmArgs g{}; g.A = l.X; g.lda = l.ldx; g.B = dY; g.ldb = ldg; g.C = partial; g.ldc = l.out; g.M = l.in; g.N = l.out; g.K = (int)M;
             g.k_chunk = FLEX_SPLIT; g.split_stride = (long long)l.in * l.out; g.colsum = colsum;
-            launch_gemm(st, false, g, n_split);
+            g.precision = t->precision; launch_gemm(st, false, g, n_split);
             reduce(partial, (long long)l.in * l.out, l.w, colsum, l.out, l.b);
         }
         if (l.bwt >= 0) {                                                    // a reader of a branch's output: its term, in the order this loop meets the readers
@@ -745,7 +745,7 @@ void FlexBackend::network_backward(long long M, hipStream_t st) {
         GemmArgs g{}; g.A = dY; g.lda = ldg; g.B = wt + l.wt; g.ldb = l.in - l.enc; g.C = dX; g.ldc = ldg; g.M = (int)M; g.N = l.in - l.enc; g.K = l.out;
         g.accumulate = accumulate;
         if (s.relu) { g.mask = s.Y; g.ldmask = s.ldy; }
-        launch_gemm(st, true, g);
+        g.precision = t->precision; launch_gemm(st, true, g);
         cur ^= 1;
     }
 }

@@ -8,30 +8,12 @@
 // aligned, element by element with bounds otherwise) while the current ones, already in LDS as As[p][i] / Bs[p][j], feed the MFMAs; one
 // barrier per panel (double buffered).  The f32 MFMA shares the vector ALUs' lanes, so every VALU instruction of the loop
 // costs MFMA time: hence the vector loads and the branch-free interior path.
+// GemmArgs::precision = NTX_PRECISION_BF16X6 sends the same tiles, grid and arguments to the second body, ntx_gemm_bf16x6.hip (six bf16 products
+// on the 16-bit MFMAs); what the two bodies share -- the epilogue, the column sums' ordered tail, the tile numbering -- is ntx_gemm_device.h.
 #include <algorithm>
 #include <type_traits>
-#include "ntx_trainer.h"
-#include "ntx_train_device.h"   // f32x2, f32x4, f32x16
+#include "ntx_gemm_device.h"   // fetch_run, gemm_epilogue, gemm_colsum_sum, gemm_place: shared with the bf16x6 body
 namespace ntx_train {
-constexpr int TM = 128;
-
-// n consecutive floats of a row into registers: 16-byte loads, or one by one under a bound
-template <int n, bool FAST>
-__device__ __forceinline__ void fetch_run(const float *g, bool row_ok, int first, int bound, float *r, bool aligned_ok = false) {
-    if (FAST) {
-        const f32x4 *v = reinterpret_cast<const f32x4 *>(g);
-#pragma unroll
-        for (int q = 0; q < n / 4; ++q) { const f32x4 x = v[q]; r[4 * q] = x.x; r[4 * q + 1] = x.y; r[4 * q + 2] = x.z; r[4 * q + 3] = x.w; }
-    } else if (row_ok && first + n <= bound && aligned_ok) {         // the run lies inside: vector loads here too
-        const f32x4 *v = reinterpret_cast<const f32x4 *>(g);
-#pragma unroll
-        for (int q = 0; q < n / 4; ++q) { const f32x4 x = v[q]; r[4 * q] = x.x; r[4 * q + 1] = x.y; r[4 * q + 2] = x.z; r[4 * q + 3] = x.w; }
-    } else {
-#pragma unroll
-        for (int q = 0; q < n; ++q) r[q] = (row_ok && first + q < bound) ? g[q] : 0.0f;
-    }
-}
-
 // TN_: columns of the workgroup's tile (128 or 256: two or four 64-wide waves across), TK_: depth of a panel; a wave always owns 64 x 64
 template <bool A_KCONTIG, int TN_, int TK_>
 __device__ __forceinline__ void gemm_body(const GemmArgs &g, int bx, int by, int bz) {
@@ -146,62 +128,15 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, int bx, int by, int
     };
     pipeline(std::true_type{}, 0, n_full);
     pipeline(std::false_type{}, n_full, n_panels);                    // a K tail; every panel of a tile on the matrix's edge
-    // D of a 32 x 32 tile: lane l, register r  <->  tile row m = 8 (r >> 2) + (r & 3) + 4 (l >> 5), tile column n = l & 31; with the
-    // interleaved tiles that is row 2 m + a, columns 2 n and 2 n + 1 (b = 0, 1): one 8-byte access per (a, r)
-    const bool whole = i0 + TM <= g.M && j0 + TN_ <= g.N && (g.ldc % 2 == 0) && (!g.mask || g.ldmask % 2 == 0) && ((uintptr_t)C % 8 == 0) && ((uintptr_t)g.mask % 8 == 0);
-    const int j = j0 + (wave % WCOLS) * 64 + 2 * (lane & 31);
-    const float bj0 = (g.bias && j < g.N) ? g.bias[j] : 0.0f, bj1 = (g.bias && j + 1 < g.N) ? g.bias[j + 1] : 0.0f;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int i = i0 + (wave / WCOLS) * 64 + 2 * (8 * (r >> 2) + (r & 3) + 4 * kh) + a;
-            float v0 = acc[a][0][r], v1 = acc[a][1][r];
-            float *c = C + (size_t)i * g.ldc + j;
-            if (whole) {
-                f32x2 *c2 = reinterpret_cast<f32x2 *>(c);
-                if (g.accumulate) { const f32x2 o = *c2; v0 += o.x; v1 += o.y; }
-                v0 += bj0; v1 += bj1;
-                if (g.relu) { v0 = v0 > 0.0f ? v0 : 0.0f; v1 = v1 > 0.0f ? v1 : 0.0f; }
-                if (g.mask) { const f32x2 mk = *reinterpret_cast<const f32x2 *>(g.mask + (size_t)i * g.ldmask + j); if (!(mk.x > 0.0f)) v0 = 0.0f; if (!(mk.y > 0.0f)) v1 = 0.0f; }
-                *c2 = f32x2{v0, v1};
-            } else if (i < g.M) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    if (j + b >= g.N) continue;
-                    float v = b ? v1 : v0;
-                    if (g.accumulate) v = v + c[b];
-                    v = v + (b ? bj1 : bj0);
-                    if (g.relu) v = v > 0.0f ? v : 0.0f;
-                    if (g.mask && !(g.mask[(size_t)i * g.ldmask + j + b] > 0.0f)) v = 0.0f;
-                    c[b] = v;
-                }
-            }
-        }
+    gemm_epilogue<TN_>(g, C, acc, i0, j0, wave, lane);
     if (want_colsum) {                                        // the panel rows a column was spread over, added up in a fixed order
         float (*red)[LROWB_] = Bs[0];
 #pragma unroll
         for (int q = 0; q < FB; ++q) red[b_row][b_off + q] = cs[q];
-        __syncthreads();
-        if ((int)threadIdx.x < TN_ && j0 + (int)threadIdx.x < g.N) {
-            float sum = 0.0f;
-            for (int q = 0; q < TK_; ++q) sum += red[q][threadIdx.x];
-            g.colsum[(size_t)bz * g.N + j0 + threadIdx.x] = sum;
-        }
+        gemm_colsum_sum<TN_, TK_, LROWB_>(g, red, j0, bz);
     }
 }
 
-// Which tile of which K range.  The tiles of ONE range read the same panels of A and B: workgroups are dealt to the 8 XCDs round-robin by
-// their linear number, each XCD has its own L2 -- so a range's tiles are given numbers that land on one XCD, next to each other in time,
-// and the panels come from HBM once instead of once per tile (dW of a 256 x 256 layer: 999 MB a launch at 3.8 TB/s before, for 537 MB of
-// operands).  lin: the workgroup's number within its problem; nx x ny tiles, nz ranges (a multiple of 8, or the plain order is kept).
-__device__ __forceinline__ void gemm_place(int lin, int nx, int ny, int nz, int &bx, int &by, int &bz) {
-    const int tiles = nx * ny;
-    if (nz % 8 == 0) {
-        const int xcd = lin & 7, slot = lin >> 3, tile = slot % tiles;
-        bz = (slot / tiles) * 8 + xcd; bx = tile % nx; by = tile / nx;
-    } else { bx = lin % nx; by = (lin / nx) % ny; bz = lin / tiles; }
-}
 template <bool A_KCONTIG, int TN_, int TK_, int WAVES_PER_EU = 2>
 __global__ __launch_bounds__(TN_ * 2) __attribute__((amdgpu_waves_per_eu(WAVES_PER_EU, 8))) void gemm_kernel(GemmArgs g) {
     int bx, by, bz;
@@ -219,7 +154,8 @@ void launch_gemm(hipStream_t st, bool a_kcontig, GemmArgs g, int n_split) {
         h.A = g.A + (a_kcontig ? (size_t)r0 * g.lda : (size_t)r0); h.C = g.C + (size_t)r0 * g.ldc; h.M = (int)std::min<long long>(rows_max, M - r0);
         if (g.mask) h.mask = g.mask + (size_t)r0 * g.ldmask;
         const dim3 grid((h.N + 127) / 128, (h.M + TM - 1) / TM, (unsigned)n_split);
-        if (a_kcontig) hipLaunchKernelGGL((gemm_kernel<true, 128, 16>), grid, dim3(256), 0, st, h);
+        if (g.precision == NTX_PRECISION_BF16X6) launch_gemm_bf16x6(st, a_kcontig, h, grid);      // the same tiles, grid and arguments: the second body
+        else if (a_kcontig) hipLaunchKernelGGL((gemm_kernel<true, 128, 16>), grid, dim3(256), 0, st, h);
         else hipLaunchKernelGGL((gemm_kernel<false, 128, 16>), grid, dim3(256), 0, st, h);
     }
 }
@@ -238,9 +174,9 @@ extern "C" int ntx_gemm_f32(const float *A, int lda, int a_kcontig, const float 
 }
 
 /* The launcher's whole argument list on caller buffers (DEVICE): every field of GemmArgs and the K split, see include/nerftex.h.  Every
- * refusal comes before the first launch.  For tests and benches of the kernel itself. */
-extern "C" int ntx_gemm_f32_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
-                               const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum, ntx_stream stream) {
+ * refusal comes before the first launch.  For tests and benches of the kernel itself; precision: the body (ntx_precision). */
+static int gemm_ex(int precision, const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
+                   const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum, ntx_stream stream) {
     if (!A || !B || !C || M < 1 || N < 1 || K < 1) return ntx_set_error(NTX_E_INVALID, "bad GEMM arguments");
     if (lda < (a_kcontig ? K : M) || ldb < N || ldc < N || (mask && ldmask < N)) return ntx_set_error(NTX_E_INVALID, "a leading dimension is smaller than its row");
     if (n_split < 1 || n_split > 65535) return ntx_set_error(NTX_E_INVALID, "n_split must be 1 .. 65535");
@@ -252,7 +188,17 @@ extern "C" int ntx_gemm_f32_ex(const float *A, int lda, int a_kcontig, const flo
     if (colsum && a_kcontig) return ntx_set_error(NTX_E_INVALID, "column sums are taken in the form A [K][M] only");
     ntx_train::GemmArgs g{}; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
     g.mask = mask; g.ldmask = ldmask; g.accumulate = accumulate; g.k_chunk = k_chunk; g.split_stride = n_split > 1 ? (long long)split_stride : 0; g.colsum = colsum;
+    g.precision = precision;
     ntx_train::launch_gemm((hipStream_t)stream, a_kcontig != 0, g, n_split);
     TRAIN_TRY(hipGetLastError());
     return NTX_OK;
+}
+extern "C" int ntx_gemm_f32_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
+                               const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum, ntx_stream stream) {
+    return gemm_ex(NTX_PRECISION_F32, A, lda, a_kcontig, B, ldb, C, ldc, M, N, K, bias, relu, mask, ldmask, accumulate, n_split, k_chunk, split_stride, colsum, stream);
+}
+/* ... and through the bf16x6 body (ntx_gemm_bf16x6.hip), on the null stream: the same refusals, the same order */
+extern "C" int ntx_gemm_bf16x6_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
+                                  const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum) {
+    return gemm_ex(NTX_PRECISION_BF16X6, A, lda, a_kcontig, B, ldb, C, ldc, M, N, K, bias, relu, mask, ldmask, accumulate, n_split, k_chunk, split_stride, colsum, nullptr);
 }

@@ -107,6 +107,8 @@ struct ntx_trainer {
     int param_depth = 0, param_width = 0;      // the parameter branches of an extended descriptor (ntx_trainer_create_flex_ex): the base struct has no room for them
     int Kp = 0, Kd = 0, P = 0;                 // features of pos_map / dir_map, parameters the model sees
     bool ipe = false; size_t n_weights = 0;    // ipe: an IntegratedPositionalEncoding model, a MipRenderer step
+    bool flex = false;                         // the layer-by-layer backend (kinds 1 and 2 of the create entries)
+    int precision = 0;                         // ntx_trainer_set_precision: the contractions of the layer-by-layer backend (NTX_PRECISION_F32 or _BF16X6)
     long long cap = 0, cap_blocks = 0, cap_rays = 0;   // samples (blocks of 32 samples, rays) the buffers hold
     float *w = nullptr, *grad = nullptr, *adam_m = nullptr, *adam_v = nullptr;
     float *stash = nullptr;                    // a second gradient (ntx_trainer_stash_gradients)
@@ -162,6 +164,7 @@ struct GemmArgs {
     int k_chunk; long long split_stride;   // blockIdx.z = z covers p in [z * k_chunk, (z + 1) * k_chunk) and writes to C + z * split_stride
     float *colsum;                   // NULL, or [n_split][N]: the column sums of B over each split's rows (the bias gradient rides along with dW)
     int aligned;                     // every row of A and B starts on a 16-byte boundary (the launcher's)
+    int precision = 0;               // ntx_precision: NTX_PRECISION_F32 (the f32 MFMA body) or NTX_PRECISION_BF16X6 (ntx_gemm_bf16x6.hip), same contract
 };
 // n_split = 1: the whole of K in one range (k_chunk = K); more: the dW form, the caller's k_chunk and split_stride.  Any M: 65 535 row tiles a launch
 void launch_gemm(hipStream_t st, bool a_kcontig, GemmArgs g, int n_split = 1);

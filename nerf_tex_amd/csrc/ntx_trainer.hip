@@ -251,7 +251,7 @@ static int trainer_create(int kind, const ntx_model_desc *desc, const float *wei
     if (!flex && (rc = count_ok()) != NTX_OK) return rc;
     ntx_trainer *t = new ntx_trainer();
     t->device = device; t->desc = dm.desc; t->ipe = dm.ipe; t->P = dm.desc.n_geo + dm.desc.n_app; t->Kp = dm.Kp; t->Kd = dm.Kd; t->n_weights = p;
-    t->param_depth = dm.param_depth; t->param_width = dm.param_width;
+    t->param_depth = dm.param_depth; t->param_width = dm.param_width; t->flex = flex;
     const long long M = (long long)max_rays * max_samples_per_ray, NB = (M + 31) / 32;
     t->cap = M; t->cap_rays = max_rays; t->cap_blocks = NB;
     DeviceMemory &mem = t->mem;
@@ -309,6 +309,21 @@ int ntx_trainer_set_iterations(ntx_trainer *t, int64_t iterations) {
     t->adam_iterations = iterations;
     return NTX_OK;
 }
+
+// The arithmetic of the layer-by-layer backend's contractions from the next step on; everything else of a step is float32 either way
+int ntx_trainer_set_precision(ntx_trainer *t, int precision) {
+    if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");
+    if (precision == NTX_PRECISION_FP16X3)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "training in fp16x3: the cotangents of a mean loss lie below the range of an IEEE half; NTX_PRECISION_BF16X6 keeps float32's exponents");
+    if (precision != NTX_PRECISION_F32 && precision != NTX_PRECISION_BF16X6) return ntx_set_error(NTX_E_INVALID, "precision %d (NTX_PRECISION_F32 or NTX_PRECISION_BF16X6)", precision);
+    if (!t->flex || t->ipe)
+        return ntx_set_error(NTX_E_UNSUPPORTED, "a precision: the fused chain (ntx_trainer_create) runs on its own float32 kernels; the layer-by-layer trainer takes the same "
+                             "model in NTX_PRECISION_BF16X6 (ntx_trainer_create_flex, ntx_trainer_create_flex_ex)");
+    if (t->pending.open) return ntx_set_error(NTX_E_INVALID, "a forward is pending: its ntx_train_backward runs in the precision of the forward; set the precision between steps");
+    t->precision = precision;
+    return NTX_OK;
+}
+int ntx_trainer_precision(const ntx_trainer *t) { return t ? t->precision : -1; }
 
 int ntx_trainer_composite_weights(ntx_trainer *t, float *weights_dev) {
     if (!t) return ntx_set_error(NTX_E_INVALID, "trainer is NULL");

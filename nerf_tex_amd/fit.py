@@ -23,18 +23,19 @@ from typing import Optional
 
 class ParameterFitter:
     def __init__(self, model, n_samples: int, max_rays: int, blur_idx: Optional[int] = None, perturb: bool = False, raw_noise_std: float = 0, map_exr: bool = False,
-                 lrate: float = 1e-2, bounds=None, device: int = 0, fused: bool = False) -> None:
+                 lrate: float = 1e-2, bounds=None, device: int = 0, fused: bool = False, precision: str = "float32") -> None:
         """`model`: the trained Nerf-Tex (`nerf_tex_amd.model.ParamNerf` container; its blob gives the weights, which never change);
         `n_samples`, `blur_idx`, `perturb`, `raw_noise_std`, `map_exr`: the renderer's, as the model was trained; `max_rays`: the largest batch
         (images x rays per image); `lrate`: Adam's; `bounds`: None or (low, high), scalars or one value per parameter -- the parameters are
         clamped to them after every update; `fused`: an 8 x 256 / skips [4] / color_depth 1 FourierFeatures model keeps the fused chain
-        (`trainer_for(..., fused=True)`), every other model trains layer by layer as without it."""
+        (`trainer_for(..., fused=True)`), every other model trains layer by layer as without it; `precision`: "float32" or "bf16x6", the
+        layer-by-layer trainer's (`Trainer.set_precision`; not together with `fused`)."""
         from .train import trainer_for
         if getattr(model, "n_params", 0) < 1:
             raise ValueError("the model has no parameters to fit (a Nerf, or n_parameters [0, 0])")
         self.model, self.lrate, self.bounds, self.device = model, float(lrate), bounds, int(device)
         self.trainer = trainer_for(model, param_gradients="only", max_rays=int(max_rays), n_samples=int(n_samples), blur_idx=blur_idx, perturb=perturb,
-                                   raw_noise_std=raw_noise_std, map_exr=map_exr, device=device, fused=fused)
+                                   raw_noise_std=raw_noise_std, map_exr=map_exr, device=device, fused=fused, precision=precision)
 
     def step(self, batch: dict, loss, parameters, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.), seed: Optional[int] = None):
         """The loss of `batch` at `parameters` [B, P] and its gradient [B, P] (GPU tensors): `batch` as `Train` takes it -- rays_o / rays_d

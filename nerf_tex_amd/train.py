@@ -27,7 +27,10 @@ torch tensors, and the step runs as `forward(...)`, the loss and its two cotange
 hands them out, `backward(d_color, d_alpha, d_weights)` takes their cotangent (`ntx_trainer_weight_cotangent`), and a callable loss that
 names `weights` (and `z_vals`) in its signature receives them.  Every trainer also takes the step through
 the INSTANCED render (`forward_instanced(bufs, ...)` on an instancer's buffers, then the same `backward`; `DifferentiableInstanceRender`):
-the layer-by-layer ones as they are, the fused chain for a FourierFeatures model once asked (`instanced=True`, `enable_instanced()`)."""
+the layer-by-layer ones as they are, the fused chain for a FourierFeatures model once asked (`instanced=True`, `enable_instanced()`).
+The layer-by-layer trainers run their contractions in float32 or, opt-in, as six bf16 products on the 16-bit matrix cores, float32-grade at
+every scale of the cotangents (`precision="bf16x6"`, `set_precision`, `ntx_trainer_set_precision`; `trainer_for(model, precision="bf16x6")`
+names them also for the chain's shape); weights, gradients, Adam and checkpoints are float32 either way."""
 
 from __future__ import annotations
 
@@ -40,7 +43,7 @@ from . import _lib
 class Trainer:
     def __init__(self, model, max_rays: int, n_samples: int, lrate: float = 5e-4, lrate_decay: float = 0, perturb: bool = True, blur_idx: Optional[int] = None,
                  map_exr: bool = False, raw_noise_std: float = 0.0, beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, device: int = 0,
-                 param_gradients=False, input_gradients=False, instanced: bool = False) -> None:
+                 param_gradients=False, input_gradients=False, instanced: bool = False, precision: str = "float32") -> None:
         """`model`: a nerf_tex_amd.model.ParamNerf container (its blob gives the initial weights); `lrate`, `lrate_decay` as train.py:49-50
         (ExponentialDecay(lrate, decay_steps=lrate_decay * 1e3, decay_rate=0.1) when lrate_decay > 0); `perturb`, `blur_idx`, `map_exr`: the
         renderer's (renderer.py:34); `raw_noise_std`: the density regulariser of map_model_output (renderer.py:190-192; config_grass_filtered_train.py:99
@@ -48,8 +51,10 @@ class Trainer:
         renders it (renderer.py:365-444): `n_samples` cone segments between n_samples + 1 depths, the parameter rows hold the blur parameter at
         `blur_idx` (required) -- its product with cone_scale is the cone's radius, and the model sees the other parameters.
         `param_gradients` / `input_gradients`: False, True or "only" (`set_gradients`), for a FourierFeatures model.  `instanced`: the trainer
-        also takes steps through the instanced render (`enable_instanced`, `forward_instanced`), for a FourierFeatures model."""
+        also takes steps through the instanced render (`enable_instanced`, `forward_instanced`), for a FourierFeatures model.  `precision`:
+        "float32", or "bf16x6" (`set_precision`) on the layer-by-layer trainers; the fused chain refuses it (NTX_E_UNSUPPORTED)."""
         import numpy as np
+        _train_precision(precision)
         self.mip = getattr(model, "pos_encoding", "fourier") == "ipe"
         if self.mip and blur_idx is None:
             raise ValueError("an IPE model trains as the MipRenderer renders it, which needs blur_idx (renderer.py:385 indexes the parameters with it)")
@@ -79,6 +84,9 @@ class Trainer:
         self._last_rays = 0
         self._pending, self._forwards = None, 0                                 # (serial, rays, device tensors, samples a ray) of a `forward` whose `backward` has not run
         self.param_gradients = self.input_gradients = False
+        self.precision = "float32"
+        if precision != "float32":
+            self.set_precision(precision)
         if param_gradients is not False or input_gradients is not False:
             self.set_gradients(param_gradients, input_gradients)
         if instanced:
@@ -114,6 +122,8 @@ class Trainer:
             ds = cfg.get("train_dataset_config") or {}
             max_rays = int(cfg.get("batchsize", ds.get("batchsize", 1))) * int(cfg.get("rays_per_image", (ds.get("pixel_sampler_config") or {}).get("n_samples", 1024)))
         kw = dict(max_rays=max_rays, n_samples=n_samples, lrate=cfg.get("lrate", 5e-4), lrate_decay=cfg.get("lrate_decay", 0), device=device, **known)
+        if cfg.get("precision") not in (None, "float32"):                          # a top-level key of the config: "bf16x6" trains layer by layer
+            kw["precision"] = cfg["precision"]
         if mip and n_importance > 0:
             raise NotImplementedError("Importance sampling for mip-NeRF style rendering is not implemented in the reference either (renderer.py:403-404)")
         if mip != (getattr(model, "pos_encoding", "fourier") == "ipe"):             # the render side's pairing (renderer.py:71, :338)
@@ -127,6 +137,15 @@ class Trainer:
         if h is not None and h.value and _lib is not None and getattr(_lib, "lib", None) is not None:
             _lib.lib.ntx_trainer_destroy(h)
             self._h = None
+
+    def set_precision(self, name: str) -> None:
+        """The arithmetic of the layer-by-layer trainers' contractions from the next step on (`ntx_trainer_set_precision`): "float32", or
+        "bf16x6" -- both operands of every Dense layer's product, forward and backward, as three bf16 terms and six products on the 16-bit
+        matrix cores, float32-grade at every scale of the cotangents.  Weights, gradients, Adam and checkpoints are float32 either way.
+        Refused by the fused chain (NTX_E_UNSUPPORTED) and between a `forward` and its `backward` (NTX_E_INVALID); the trainer keeps what
+        it had."""
+        _lib.check(_lib.lib.ntx_trainer_set_precision(self._h, _train_precision(name)))
+        self.precision = str(name)
 
     def _vector(self, what: int):
         import numpy as np
@@ -673,6 +692,15 @@ class BranchTrainer(FlexTrainer):
         return out
 
 
+def _train_precision(name) -> int:
+    """The ntx_precision of a trainer's precision name."""
+    if not isinstance(name, str) or name not in _lib.TRAIN_PRECISIONS:
+        if name == "fp16x3":
+            raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "training in fp16x3: the cotangents of a mean loss lie below the range of an IEEE half; \"bf16x6\" keeps float32's exponents")
+        raise ValueError(f"precision must be one of {sorted(_lib.TRAIN_PRECISIONS)}, not {name!r}")
+    return _lib.TRAIN_PRECISIONS[name]
+
+
 def _chain_takes(model) -> bool:
     """Whether `Trainer` (the fused chain, `ntx_trainer_create`) trains `model`: ParamNerf 8 x 256 / skips [4] / color_depth 1 with Fourier
     features or IPE and encodings of at most 96 features, or a narrower Fourier network that `_widened` pads into it."""
@@ -688,16 +716,22 @@ def _chain_takes(model) -> bool:
     return _widened(model) is not None and model.n_pos == 3
 
 
-def trainer_class_for(model, branches: bool = False, param_gradients=False, input_gradients=False, fused: bool = False):
+def trainer_class_for(model, branches: bool = False, param_gradients=False, input_gradients=False, fused: bool = False, precision: str = "float32"):
     """The class that trains `model`, without creating anything (no device is asked for): `Trainer` where the fused chain takes it,
     `FlexTrainer` for any other model `ntx_trainer_create_flex` accepts; the library's NTX_E_UNSUPPORTED otherwise -- which is what a
     model with parameter branches gets unless `branches` is set: then a model with param_depth > 0 and at least one parameter gets
     `BranchTrainer`, if `ntx_trainer_create_flex_ex` accepts it.  `param_gradients` / `input_gradients` (True or "only"): the layer-by-layer class also
     where the chain would take the model, unless `fused` is set: then a FourierFeatures model the chain takes keeps `Trainer`, which takes both
     gradients through `ntx_trainer_enable_gradients` (an IPE model: the library's NTX_E_UNSUPPORTED -- the cone gaussians' derivative is not
-    written, and the layer-by-layer trainer takes no IPE model)."""
+    written, and the layer-by-layer trainer takes no IPE model).  `precision` "bf16x6": the layer-by-layer class also for the chain's own
+    8 x 256 shape (the chain runs on its own float32 kernels); together with `fused` it raises NTX_E_UNSUPPORTED."""
     import numpy as np
     wants = param_gradients is not False or input_gradients is not False
+    if _train_precision(precision) != _lib.PRECISION_F32:
+        if fused:
+            raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, f"precision {precision!r} on the fused chain (fused=True): the chain runs on its own float32 kernels; the "
+                                "layer-by-layer trainer takes the same model")
+        wants = True
     if _chain_takes(model) and (not wants or fused):
         if wants and model.pos_encoding == "ipe":
             raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "parameter / input gradients of an IPE model on the fused chain: the cone gaussians' derivative is not written")
@@ -718,7 +752,8 @@ def trainer_for(model, **kw):
     model the chain takes, the fused chain with the same two keywords.  `instanced=True` goes on to the class: the chain then takes instanced
     steps too (the layer-by-layer classes always do)."""
     fused = bool(kw.pop("fused", False))
-    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False), input_gradients=kw.get("input_gradients", False), fused=fused)
+    cls = trainer_class_for(model, branches=True, param_gradients=kw.get("param_gradients", False), input_gradients=kw.get("input_gradients", False), fused=fused,
+                            precision=kw.get("precision", "float32"))
     if cls is Trainer and not fused:
         kw.pop("param_gradients", None)                                        # (False: the chain has no such argument)
         kw.pop("input_gradients", None)
@@ -918,7 +953,8 @@ def _split_blob(table, blob):
 
 def Train(target_path: str, train_dataset=None, val_dataset=None, model_config: dict = None, loss_config: dict = None, n_iters: int = 1000, lrate: float = 5e-4,
           lrate_decay: float = 0, renderer_config: dict = None, logger_config: dict = None, max_rays: int = None, device: int = 0, weights=None,
-          composite_bkgd: bool = None, bkgd_color=None, train_dataset_config: dict = None, val_dataset_config: dict = None, **kwargs) -> dict:
+          composite_bkgd: bool = None, bkgd_color=None, train_dataset_config: dict = None, val_dataset_config: dict = None, precision: str = "float32",
+          **kwargs) -> dict:
     """network.train.Train (train.py:7-70).  The data side either as the reference's blocks -- `train_dataset_config` / `val_dataset_config`
     (`network.dataset.Dataset` over `TFRecord` / `FileFolder` / `GenerateData`, instantiated here as train.py:23-26 does, `n_parameters` of the
     model defaulting to the dataset's, :29) -- or handed in: `train_dataset` any iterable of batch dicts as network/dataset.py maps them
@@ -926,7 +962,8 @@ def Train(target_path: str, train_dataset=None, val_dataset=None, model_config: 
     `nerf_tex_amd.dataset.Dataset` (or any iterable of ray batch dicts with height / width / composite_bkgd / bkgd_color) whose views are
     rendered every `i_img` steps.  The other arguments are the reference's: `model_config` / `loss_config` /
     `renderer_config` blocks, `n_iters`, `lrate`, `lrate_decay`, and of `logger_config` (logger.py:14) `i_print`, `i_img`, `i_checkpoint`,
-    `max_to_keep`.  What the reference's Logger does at its cadences happens here: a checkpoint `checkpoints/ckpt-<step>` under `target_path`
+    `max_to_keep`; `precision` (this package's; a config's top-level key): "float32", or "bf16x6" -- the layer-by-layer trainer with its
+    contractions on the 16-bit matrix cores (`Trainer.set_precision`).  What the reference's Logger does at its cadences happens here: a checkpoint `checkpoints/ckpt-<step>` under `target_path`
     (model + step + optimizer, train.py:55-57) every `i_checkpoint` steps, the validation views through `Renderer` (`MipRenderer` for a mip run) -- the inference path, the
     trainer's weights handed over on the device -- every `i_img` steps; a run whose `target_path` holds checkpoints resumes from the newest and
     takes `n_iters - step` batches (train.py:60).  Returns {'trainer', 'renderer', 'loss' [(step, value)], 'images' {step: [RGBA [H,W,4]]},
@@ -950,7 +987,7 @@ def Train(target_path: str, train_dataset=None, val_dataset=None, model_config: 
         model_config = dict(model_config)
         model_config.setdefault("n_parameters", train_dataset.n_parameters)     # train.py:29
     cfg = util.remap_reference_config(dict(model_config=model_config, loss_config=loss_config, renderer_config=renderer_config or {}, lrate=lrate,
-                                           lrate_decay=lrate_decay))
+                                           lrate_decay=lrate_decay, precision=precision))
     if max_rays is None:
         if hasattr(train_dataset, "batchsize") and hasattr(train_dataset, "n_samples"):
             max_rays = int(train_dataset.batchsize) * int(train_dataset.n_samples)
