@@ -894,6 +894,50 @@ int ntx_trainer_precision(const ntx_trainer *t);
 int ntx_gemm_bf16x6_ex(const float *A, int lda, int a_kcontig, const float *B, int ldb, float *C, int ldc, int M, int N, int K, const float *bias, int relu,
                        const float *mask, int ldmask, int accumulate, int n_split, int k_chunk, int64_t split_stride, float *colsum);
 
+/* Rays from camera poses that live on the device (ABI v7, appended): ntx_generate_rays_at for a BATCH of cameras, the first half of camera
+ * pose fitting -- the rays of a training batch (say 4 images x 256 rays) in one launch, with no host round trip for the poses an optimiser
+ * keeps on the device.
+ *   poses            DEVICE float [n_poses][3][4]: the top three rows of every c2w, row-major
+ *   focal            DEVICE float [n_poses]
+ *   image_plane_loc  DEVICE float [n_rays][2] = (row, col), as ntx_generate_rays_at takes it
+ *   rays_per_pose    ray k belongs to pose k / rays_per_pose; the last pose may have fewer rays; n_poses = ceil(n_rays / rays_per_pose)
+ * height, width, mode (0: Proxy with the HOST float[3] b0 / b1; 1: Frustum with near_t / far_t) and the four DEVICE outputs rays_o[n,3],
+ * rays_d[n,3], t[n,2], cone_scale[n,1] are ntx_generate_rays_at's.  No pose, focal or location is read from the host; the call waits for
+ * nothing and allocates nothing.  The arithmetic of a ray is the ONE device function ntx_generate_rays_at's kernel runs, in its float32
+ * order: with the same matrix and focal the four outputs are ntx_generate_rays_at's bit for bit.
+ * `stream`: a hipStream_t passed as void*, with the meaning of every other entry's `ntx_stream` (NULL = the null stream; the launch is queued
+ * on it and nothing else is touched).
+ * NTX_E_INVALID, all before the launch: a NULL buffer; height, width <= 0 or n_rays < 0; a mode outside 0..1; n_poses < 1 (or >= 2^31);
+ * rays_per_pose < 1; n_rays > 0 and n_poses != ceil(n_rays / rays_per_pose); b0 or b1 NULL in mode 0.  n_rays = 0 (with otherwise valid
+ * arguments): NTX_OK and no launch. */
+int ntx_generate_rays_posed(const float *poses, const float *focal, int64_t n_poses, int height, int width, const float *image_plane_loc, int64_t n_rays,
+                            int64_t rays_per_pose, int mode, const float *b0, const float *b1, float near_t, float far_t, float *rays_o, float *rays_d, float *t,
+                            float *cone_scale, void *stream /* hipStream_t */);
+/* The adjoint of that map (ABI v7, appended): from the cotangents d_rays_o, d_rays_d (DEVICE [n_rays][3]; what a trainer's
+ * ntx_trainer_ray_gradients leaves) to d_poses (DEVICE [n_poses][3][4]) and d_focal (DEVICE [n_poses]) -- what connects a camera to the ray
+ * gradients that ntx_trainer_enable_input_gradients / ntx_trainer_enable_gradients document for "camera or pose refinement".  The first nine
+ * arguments are ntx_generate_rays_posed's.  With (li, lj) a ray's location, f its pose's focal and R the pose's 3x3:
+ *     dc = (d0, d1, -1),  d0 = (lj + 0.5 - width / 2) / f,  d1 = -(li + 0.5 - height / 2) / f      (ray_sampler.py:41)
+ *     v = R dc,  n = v / |v|,  g_o = d_rays_o[k],  g_d = d_rays_d[k]
+ *     mode 0 (rays_d = n):  g_v = (g_d - n (n . g_d)) / |v|          mode 1 (rays_d = v):  g_v = g_d
+ *     d_poses[p][r][c] = sum_k g_v[r] dc[c]   (c < 3: dL/dR)          d_poses[p][r][3] = sum_k g_o[r]   (dL/dT)
+ *     d_focal[p] = -(1 / f) sum_k g_v . (d0 R[:,0] + d1 R[:,1])
+ * the sums over the rays k of pose p.  HELD CONSTANT: t and cone_scale -- the convention of ntx_trainer_enable_input_gradients, where the
+ * depths, tnear_far and cone_scale take no gradient; so the proxy's bounds are not among the arguments, and the focal's gradient is the one
+ * through the ray directions alone.  The pose is differentiated as twelve free numbers: keeping R a rotation is the caller's parametrisation.
+ * The sums of a pose run in a fixed order of the pose's OWN: lane i of 1024 adds the terms of the pose's rays i, i + 1024, ... in ascending
+ * order (T = 1024 partial sums), a butterfly adds the 64 lanes of each wave and a binary tree the 16 waves.  The result is bit-reproducible and
+ * does not depend on n_poses, on where the pose stands in the batch or on the grid: one workgroup per pose, one pass, no atomics, no scratch
+ * and no allocation.  A ray whose d_rays_d is exactly zero adds exact zeros to dR and d_focal whatever its direction holds, one whose
+ * d_rays_o is zero adds exact zeros to dT: rays that missed (a trainer leaves exact zeros there) change no bit.  EVERY entry of d_poses and
+ * d_focal is written -- +0.0 for a pose whose cotangents are all zero, and for every pose when n_rays = 0 (then n_poses >= 1 is all that is
+ * asked of it).
+ * `stream`: as above.  NTX_E_INVALID, all before the launch: as above, without the bounds.  Out of scope: gradients through t, the depths
+ * and cone_scale; lens distortion and principal point; second order. */
+int ntx_generate_rays_posed_adjoint(const float *poses, const float *focal, int64_t n_poses, int height, int width, const float *image_plane_loc, int64_t n_rays,
+                                    int64_t rays_per_pose, int mode, const float *d_rays_o, const float *d_rays_d, float *d_poses, float *d_focal,
+                                    void *stream /* hipStream_t */);
+
 #ifdef __cplusplus
 }
 #endif

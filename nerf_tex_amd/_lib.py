@@ -180,6 +180,9 @@ SYMBOLS = {
     "ntx_trainer_set_precision": (C.c_int, [_vp, C.c_int]),
     "ntx_trainer_precision": (C.c_int, [_vp]),
     "ntx_gemm_bf16x6_ex": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _vp]),
+    "ntx_generate_rays_posed": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int, _fp, _fp, C.c_float, C.c_float,
+                                          _vp, _vp, _vp, _vp, _vp]),
+    "ntx_generate_rays_posed_adjoint": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

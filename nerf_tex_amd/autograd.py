@@ -95,6 +95,60 @@ class DifferentiableInstanceRender:
                                         dict(self.opts, **kw))
 
 
+def __getattr__(name):
+    """`nerf_tex_amd.autograd.PosedRays`: the torch.autograd.Function of `ray_sampler.posed_rays`, made at its first use."""
+    if name == "PosedRays":
+        return _posed_rays_function()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+@functools.lru_cache(maxsize=None)
+def _posed_rays_function():
+    """The torch.autograd.Function in front of the render op when the CAMERAS are the unknowns: rays from device poses
+    (`ntx_generate_rays_posed`) forward, `ntx_generate_rays_posed_adjoint` backward.
+
+        rays_o, rays_d, t, cone_scale = PosedRays.apply(poses [B,3,4], focal [B], image_plane_loc [N,2], rays_per_pose, consts)
+
+    with consts = (height, width, mode, b_0, b_1, near, far) (`ray_sampler.posed_rays` builds them).  All tensors float32, contiguous, on one
+    GPU; both launches go to the current stream.  `poses` and `focal` receive gradients when they require them; t and cone_scale are marked
+    non-differentiable (the depths and the cone take no gradient anywhere in the step: include/nerftex.h).  First order only."""
+    import torch
+    from . import _lib
+
+    class PosedRays(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, poses, focal, loc, rays_per_pose, consts):
+            height, width, mode, b0, b1, near, far = consts
+            n, dev = int(loc.shape[0]), poses.device
+            poses, focal = poses.detach(), focal.detach()
+            rays_o, rays_d = torch.empty((n, 3), device=dev, dtype=torch.float32), torch.empty((n, 3), device=dev, dtype=torch.float32)
+            t, cone = torch.empty((n, 2), device=dev, dtype=torch.float32), torch.empty((n, 1), device=dev, dtype=torch.float32)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib.ntx_generate_rays_posed(poses.data_ptr(), focal.data_ptr(), int(poses.shape[0]), height, width, loc.data_ptr(), n, int(rays_per_pose), mode,
+                                                            _lib.f3(b0) if b0 is not None else None, _lib.f3(b1) if b1 is not None else None, near, far,
+                                                            rays_o.data_ptr(), rays_d.data_ptr(), t.data_ptr(), cone.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            ctx.save_for_backward(poses, focal, loc)
+            ctx.call = (height, width, int(rays_per_pose), mode)
+            ctx.mark_non_differentiable(t, cone)
+            return rays_o, rays_d, t, cone
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, d_rays_o, d_rays_d, _d_t, _d_cone):
+            poses, focal, loc = ctx.saved_tensors
+            height, width, rays_per_pose, mode = ctx.call
+            n, dev = int(loc.shape[0]), poses.device
+            d_rays_o, d_rays_d = d_rays_o.to(torch.float32).contiguous(), d_rays_d.to(torch.float32).contiguous()
+            d_poses, d_focal = torch.empty_like(poses), torch.empty_like(focal)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib.ntx_generate_rays_posed_adjoint(poses.data_ptr(), focal.data_ptr(), int(poses.shape[0]), height, width, loc.data_ptr(), n, rays_per_pose, mode,
+                                                                    d_rays_o.data_ptr(), d_rays_d.data_ptr(), d_poses.data_ptr(), d_focal.data_ptr(),
+                                                                    torch.cuda.current_stream(dev).cuda_stream))
+            return (d_poses if ctx.needs_input_grad[0] else None), (d_focal if ctx.needs_input_grad[1] else None), None, None, None
+
+    return PosedRays
+
+
 @functools.lru_cache(maxsize=None)
 def _render_function():
     """The torch.autograd.Function behind `DifferentiableRender` (made at the first call: importing the package does not import torch)."""

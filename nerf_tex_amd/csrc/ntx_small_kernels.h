@@ -58,11 +58,17 @@ __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) {
 // ---------------------------------------------------------------------------------------------
 // ray generation (pixel_sampler.py:14-15, ray_sampler.py:23-48, proxy.py:13-35)
 // ---------------------------------------------------------------------------------------------
+struct RaygenConsts {                 // what every ray of a launch shares beside its camera
+    float b0[3], b1[3];
+    float half_w, half_h, near_t, far_t;
+    int mode;
+};
+
 struct RaygenArgs {
     float c2w[16];
-    float b0[3], b1[3];
-    float focal, half_w, half_h, near_t, far_t;
-    int width, mode;
+    RaygenConsts k;                   // b0 / b1, half_w / half_h, near_t / far_t, mode
+    float focal;
+    int width;
     int64_t pixel0, n;
     int64_t run_length, run_stride;   // local ray k = pixel pixel0 + (k / run_length) * run_stride + k % run_length
     const float *loc;                 // NULL, or image_plane_loc [n,2] = (row, col) of every ray as float32 (any pixel sampler)
@@ -90,6 +96,37 @@ NTX_DEV void aabb_t(const float (&ro)[3], const float (&rd)[3], const float (&b0
     t1 = hit ? tmin : __builtin_inff();
 }
 
+// ray_sampler.rays_from_camera (ray_sampler.py:39-48) + Proxy (:32-37) / Frustum (:15-21) for ONE ray at the image-plane location (li, lj) =
+// (row, col): the one statement of the generator's float32 arithmetic, shared by raygen_kernel (a camera in the kernel's arguments) and
+// raygen_posed_kernel (cameras in device memory).  m: the top three rows of c2w, row-major with a row stride of 4.
+NTX_DEV void raygen_ray(const float *m, float focal, const RaygenConsts &c, float li, float lj, int64_t k, float *rays_o, float *rays_d, float *t, float *cone_out) {
+    const float d0 = (lj + 0.5f - c.half_w) / focal;                         // ray_sampler.py:41
+    const float d1 = -(li + 0.5f - c.half_h) / focal;
+    const float d2 = -1.0f;
+    float rd[3], ro[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        rd[r] = (d0 * m[4 * r + 0] + d1 * m[4 * r + 1]) + d2 * m[4 * r + 2];   // :42
+        ro[r] = m[4 * r + 3];                                                    // :43
+    }
+    const float nxy = __builtin_sqrtf(d0 * d0 + d1 * d1);
+    const float nrm = __builtin_sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+    const float cone = cosf(atanf(nxy)) / nrm / focal;                          // :46
+    float t0, t1;
+    if (c.mode == 0) {
+        const float n = __builtin_sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);  // :34
+#pragma unroll
+        for (int r = 0; r < 3; ++r) rd[r] = rd[r] / n;
+        aabb_t(ro, rd, c.b0, c.b1, t0, t1);
+    } else {
+        t0 = c.near_t; t1 = c.far_t;
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { rays_o[3 * k + r] = ro[r]; rays_d[3 * k + r] = rd[r]; }
+    t[2 * k] = t0; t[2 * k + 1] = t1;
+    cone_out[k] = cone;
+}
+
 __global__ __launch_bounds__(256) void raygen_kernel(RaygenArgs a) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.n) return;
@@ -99,31 +136,114 @@ __global__ __launch_bounds__(256) void raygen_kernel(RaygenArgs a) {
         const int64_t pix = a.pixel0 + (k / a.run_length) * a.run_stride + k % a.run_length;
         li = (float)(pix / a.width); lj = (float)(pix % a.width);
     }
-    const float d0 = (lj + 0.5f - a.half_w) / a.focal;                       // ray_sampler.py:41
-    const float d1 = -(li + 0.5f - a.half_h) / a.focal;
-    const float d2 = -1.0f;
-    float rd[3], ro[3];
+    raygen_ray(a.c2w, a.focal, a.k, li, lj, k, a.rays_o, a.rays_d, a.t, a.cone);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rays of a BATCH of cameras that live on the device (ntx_generate_rays_posed) and the adjoint of that map (ntx_generate_rays_posed_adjoint):
+// ray k belongs to pose k / rays_per_pose.  poses [n_poses][3][4] (the top three rows of c2w, a row stride of 4 as in RaygenArgs::c2w),
+// focal [n_poses].  The forward is raygen_ray per thread.
+// ---------------------------------------------------------------------------------------------
+struct RaygenPosedArgs {
+    RaygenConsts k;
+    const float *poses, *focal, *loc;
+    int64_t n, rays_per_pose;
+    float *rays_o, *rays_d, *t, *cone;
+};
+
+__global__ __launch_bounds__(256) void raygen_posed_kernel(RaygenPosedArgs a) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    const int64_t p = k / a.rays_per_pose;
+    raygen_ray(a.poses + 12 * p, a.focal[p], a.k, a.loc[2 * k], a.loc[2 * k + 1], k, a.rays_o, a.rays_d, a.t, a.cone);
+}
+
+// The adjoint: ONE workgroup of POSED_ADJ_THREADS per pose.  Thread i adds the terms of the pose's rays i, i + POSED_ADJ_THREADS, ... in
+// ascending order into 13 partial sums (dR 3x3, dT 3, the focal's sum), a butterfly adds the 64 lanes of a wave, a binary tree in LDS the
+// waves: the order is a function of the pose's OWN ray count alone -- bit-reproducible, independent of n_poses, of the pose's place in the
+// batch and of the grid; no atomics.  dc = (d0, d1, -1), v = R dc as the forward forms them (the same float32 expressions):
+//     mode 0: g_v = (g_d - n (n . g_d)) / |v|, n = v / |v|;   mode 1: g_v = g_d
+//     dR[r][c] += g_v[r] dc[c];   dT[r] += g_o[r];   s += g_v . (d0 R[:,0] + d1 R[:,1]);   d_focal = -(s / f)
+// t and cone_scale are constants.  A ray whose g_d is exactly zero adds exact zeros whatever its direction is.
+constexpr int POSED_ADJ_THREADS = 1024;
+constexpr int POSED_ADJ_SUMS = 13;
+
+struct RaygenPosedAdjointArgs {
+    const float *poses, *focal, *loc, *d_rays_o, *d_rays_d;
+    float half_w, half_h;
+    int mode;
+    int64_t n, rays_per_pose;
+    float *d_poses, *d_focal;
+};
+
+__global__ __launch_bounds__(POSED_ADJ_THREADS) void raygen_posed_adjoint_kernel(RaygenPosedAdjointArgs a) {
+    __shared__ float part[POSED_ADJ_THREADS / 64][POSED_ADJ_SUMS];
+    const int64_t p = blockIdx.x;
+    const int64_t first = p * a.rays_per_pose;
+    const int64_t left = a.n - first;
+    const int64_t count = left < a.rays_per_pose ? (left > 0 ? left : 0) : a.rays_per_pose;
+    const float *m = a.poses + 12 * p;
+    const float f = a.focal[p];
+    float R[3][3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        rd[r] = (d0 * a.c2w[4 * r + 0] + d1 * a.c2w[4 * r + 1]) + d2 * a.c2w[4 * r + 2];   // :42
-        ro[r] = a.c2w[4 * r + 3];                                                            // :43
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = m[4 * r + c];
+    float acc[POSED_ADJ_SUMS];
+#pragma unroll
+    for (int j = 0; j < POSED_ADJ_SUMS; ++j) acc[j] = 0.0f;
+    for (int64_t i = threadIdx.x; i < count; i += POSED_ADJ_THREADS) {
+        const int64_t k = first + i;
+        const float li = a.loc[2 * k], lj = a.loc[2 * k + 1];
+        const float go[3] = {a.d_rays_o[3 * k], a.d_rays_o[3 * k + 1], a.d_rays_o[3 * k + 2]};
+        const float gd[3] = {a.d_rays_d[3 * k], a.d_rays_d[3 * k + 1], a.d_rays_d[3 * k + 2]};
+        const float dc[3] = {(lj + 0.5f - a.half_w) / f, -(li + 0.5f - a.half_h) / f, -1.0f};
+        float gv[3] = {gd[0], gd[1], gd[2]};
+        const bool zero = gd[0] == 0.0f && gd[1] == 0.0f && gd[2] == 0.0f;
+        if (a.mode == 0 && !zero) {
+            float v[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) v[r] = (dc[0] * R[r][0] + dc[1] * R[r][1]) + dc[2] * R[r][2];
+            const float len = __builtin_sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+            const float nv[3] = {v[0] / len, v[1] / len, v[2] / len};
+            const float dot = (nv[0] * gd[0] + nv[1] * gd[1]) + nv[2] * gd[2];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) gv[r] = (gd[r] - nv[r] * dot) / len;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[3 * r + c] += gv[r] * dc[c];
+            acc[9 + r] += go[r];
+        }
+        float s = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) s += gv[r] * (dc[0] * R[r][0] + dc[1] * R[r][1]);
+        acc[12] += s;
     }
-    const float nxy = __builtin_sqrtf(d0 * d0 + d1 * d1);
-    const float nrm = __builtin_sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-    const float cone = cosf(atanf(nxy)) / nrm / a.focal;                                    // :46
-    float t0, t1;
-    if (a.mode == 0) {
-        const float n = __builtin_sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);  // :34
 #pragma unroll
-        for (int r = 0; r < 3; ++r) rd[r] = rd[r] / n;
-        aabb_t(ro, rd, a.b0, a.b1, t0, t1);
-    } else {
-        t0 = a.near_t; t1 = a.far_t;
+    for (int j = 0; j < POSED_ADJ_SUMS; ++j)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc[j] += __shfl_xor(acc[j], d, 64);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < POSED_ADJ_SUMS; ++j) part[wv][j] = acc[j];
     }
+    __syncthreads();
+    if (threadIdx.x < POSED_ADJ_SUMS) {
+        const int j = threadIdx.x;
+        float w[POSED_ADJ_THREADS / 64];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { a.rays_o[3 * k + r] = ro[r]; a.rays_d[3 * k + r] = rd[r]; }
-    a.t[2 * k] = t0; a.t[2 * k + 1] = t1;
-    a.cone[k] = cone;
+        for (int q = 0; q < POSED_ADJ_THREADS / 64; ++q) w[q] = part[q][j];
+#pragma unroll
+        for (int h = POSED_ADJ_THREADS / 128; h >= 1; h >>= 1)
+#pragma unroll
+            for (int q = 0; q < h; ++q) w[q] += w[q + h];
+        if (j < 9) a.d_poses[12 * p + 4 * (j / 3) + j % 3] = w[0];
+        else if (j < 12) a.d_poses[12 * p + 4 * (j - 9) + 3] = w[0];
+        else a.d_focal[p] = w[0] == 0.0f ? 0.0f : -(w[0] / f);                  // (a zero sum gives +0, not -(0 / f) = -0)
+    }
 }
 
 // proxy.AABB.__call__ on the caller's own rays (proxy.py:13-35): thread per ray

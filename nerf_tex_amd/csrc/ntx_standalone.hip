@@ -6,17 +6,25 @@
 
 using namespace ntx;
 
+// what the rays of one launch share beside their camera
+static RaygenConsts raygen_consts(int height, int width, int mode, const float *b0, const float *b1, float near_t, float far_t) {
+    RaygenConsts k{};
+    if (mode == 0) { memcpy(k.b0, b0, sizeof(k.b0)); memcpy(k.b1, b1, sizeof(k.b1)); }
+    k.half_w = (float)(.5 * width);   // `.5 * width` is evaluated by python, then cast (ray_sampler.py:41)
+    k.half_h = (float)(.5 * height);
+    k.near_t = near_t; k.far_t = far_t;
+    k.mode = mode;
+    return k;
+}
+
 // the generator's launch for n rays: pixels pixel0 .. in runs (loc NULL), or the image-plane locations loc[n][2]
 static int launch_raygen(const float *c2w, int height, int width, float focal, int64_t pixel0, int64_t n, int64_t run_length, int64_t run_stride, const float *loc, int mode,
                          const float *b0, const float *b1, float near_t, float far_t, float *rays_o, float *rays_d, float *t, float *cone_scale, ntx_stream stream) {
     RaygenArgs a{};
     memcpy(a.c2w, c2w, sizeof(a.c2w));
-    if (mode == 0) { memcpy(a.b0, b0, sizeof(a.b0)); memcpy(a.b1, b1, sizeof(a.b1)); }
+    a.k = raygen_consts(height, width, mode, b0, b1, near_t, far_t);
     a.focal = focal;
-    a.half_w = (float)(.5 * width);   // `.5 * width` is evaluated by python, then cast (ray_sampler.py:41)
-    a.half_h = (float)(.5 * height);
-    a.near_t = near_t; a.far_t = far_t;
-    a.width = width; a.mode = mode;
+    a.width = width;
     a.pixel0 = pixel0; a.n = n;
     a.run_length = run_length; a.run_stride = run_stride;
     a.loc = loc;
@@ -72,6 +80,52 @@ int ntx_generate_rays_at(const float *c2w, int height, int width, float focal, c
     if (n_rays == 0) return NTX_OK;
     if (!image_plane_loc) return ntx_set_error(NTX_E_INVALID, "image_plane_loc is NULL");
     return launch_raygen(c2w, height, width, focal, 0, n_rays, 1, 1, image_plane_loc, mode, b0, b1, near_t, far_t, rays_o, rays_d, t, cone_scale, stream);
+}
+
+// the argument checks the two posed entries share: the cameras, the image size and the split of the rays over the poses
+static int check_posed(const float *poses, const float *focal, int64_t n_poses, int height, int width, const float *image_plane_loc, int64_t n_rays, int64_t rays_per_pose,
+                       int mode) {
+    if (!poses || !focal || !image_plane_loc) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (height <= 0 || width <= 0 || n_rays < 0) return ntx_set_error(NTX_E_INVALID, "bad shape %dx%d, n_rays %lld", height, width, (long long)n_rays);
+    if (mode != 0 && mode != 1) return ntx_set_error(NTX_E_INVALID, "mode must be 0 (Proxy/AABB) or 1 (Frustum)");
+    if (n_poses < 1 || n_poses > 0x7fffffff || rays_per_pose < 1)
+        return ntx_set_error(NTX_E_INVALID, "n_poses %lld outside [1, 2^31), or rays_per_pose %lld < 1", (long long)n_poses, (long long)rays_per_pose);
+    if (n_rays > 0 && (n_rays - 1) / rays_per_pose + 1 != n_poses)
+        return ntx_set_error(NTX_E_INVALID, "%lld rays at %lld per pose are %lld poses, not %lld", (long long)n_rays, (long long)rays_per_pose,
+                             (long long)((n_rays - 1) / rays_per_pose + 1), (long long)n_poses);
+    return NTX_OK;
+}
+
+int ntx_generate_rays_posed(const float *poses, const float *focal, int64_t n_poses, int height, int width, const float *image_plane_loc, int64_t n_rays,
+                            int64_t rays_per_pose, int mode, const float *b0, const float *b1, float near_t, float far_t, float *rays_o, float *rays_d, float *t,
+                            float *cone_scale, void *stream) {
+    if (!rays_o || !rays_d || !t || !cone_scale) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (int rc = check_posed(poses, focal, n_poses, height, width, image_plane_loc, n_rays, rays_per_pose, mode)) return rc;
+    if (mode == 0 && (!b0 || !b1)) return ntx_set_error(NTX_E_INVALID, "AABB bounds are NULL");
+    if (n_rays == 0) return NTX_OK;
+    RaygenPosedArgs a{};
+    a.k = raygen_consts(height, width, mode, b0, b1, near_t, far_t);
+    a.poses = poses; a.focal = focal; a.loc = image_plane_loc;
+    a.n = n_rays; a.rays_per_pose = rays_per_pose;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.t = t; a.cone = cone_scale;
+    raygen_posed_kernel<<<dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+int ntx_generate_rays_posed_adjoint(const float *poses, const float *focal, int64_t n_poses, int height, int width, const float *image_plane_loc, int64_t n_rays,
+                                    int64_t rays_per_pose, int mode, const float *d_rays_o, const float *d_rays_d, float *d_poses, float *d_focal, void *stream) {
+    if (!d_rays_o || !d_rays_d || !d_poses || !d_focal) return ntx_set_error(NTX_E_INVALID, "NULL buffer");
+    if (int rc = check_posed(poses, focal, n_poses, height, width, image_plane_loc, n_rays, rays_per_pose, mode)) return rc;
+    RaygenPosedAdjointArgs a{};
+    a.poses = poses; a.focal = focal; a.loc = image_plane_loc; a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d;
+    a.half_w = (float)(.5 * width); a.half_h = (float)(.5 * height);
+    a.mode = mode;
+    a.n = n_rays; a.rays_per_pose = rays_per_pose;
+    a.d_poses = d_poses; a.d_focal = d_focal;
+    raygen_posed_adjoint_kernel<<<dim3((unsigned)n_poses), dim3(POSED_ADJ_THREADS), 0, (hipStream_t)stream>>>(a);   // n_rays = 0: zeros for every pose
+    HIP_TRY(hipGetLastError());
+    return NTX_OK;
 }
 
 int ntx_generate_rays(const float *c2w, int height, int width, float focal, int64_t pixel0, int64_t n_pixels,

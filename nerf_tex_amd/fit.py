@@ -14,7 +14,10 @@ returns a scalar -- a robust loss for photographs, say (`Trainer.gradients_step`
 
 `TextureFitter` fits what varies OVER a surface: the texels of the parameter textures of an instanced scene (instancer.cpp:640-667), from the
 instanced step's dL/d params_map, the texture coordinates `Instancer.sample_uv` gives per sample and the lookup restated in torch
-(`texture_lookup`, `apply_textures`)."""
+(`texture_lookup`, `apply_textures`).
+
+`PoseFitter` fits the CAMERAS: the poses (and optionally the focal lengths) the images were taken from, from the trainers' dL/d rays_o and
+dL/d rays_d through the adjoint of the ray generator (`ray_sampler.posed_rays`, `autograd.PosedRays`, `compose_poses`)."""
 
 from __future__ import annotations
 
@@ -84,6 +87,126 @@ class ParameterFitter:
     def weights(self):
         """The trainer's weights (they are the model's: no step changes them)."""
         return self.trainer.weights()
+
+
+# ---- camera poses: where was a photograph of a known material taken from? ----------------------------------------------------------------------
+
+def hat(omega):
+    """The skew matrices [B,3,3] of `omega` [B,3]: hat(w) x = w cross x."""
+    import torch
+    zero = torch.zeros_like(omega[:, 0])
+    x, y, z = omega.unbind(-1)
+    return torch.stack([torch.stack([zero, -z, y], -1), torch.stack([z, zero, -x], -1), torch.stack([-y, x, zero], -1)], -2)
+
+
+def compose_poses(c2w0, omega, tau):
+    """c2w_i = [exp(hat(omega_i)) R0_i | T0_i + tau_i], [B,4,4] in `c2w0`'s dtype: a rotation applied on the left of the initial one and a
+    shift of the camera centre.  exp is `torch.linalg.matrix_exp`, which torch differentiates, so the 3x3 block stays a rotation at every
+    omega; omega = tau = 0 gives `c2w0`'s top three rows back exactly (exp(0) is the identity matrix, and 1 * x + 0 * y = x).  The exponential
+    of the B 3x3 matrices is taken in float64 and rounded once: in float32 its scaling and squaring leaves 3e-6 of non-orthonormality at
+    |omega| of a few radians, in float64 the rounding of the result is all there is.  The last row is (0, 0, 0, 1)."""
+    import torch
+    R = torch.linalg.matrix_exp(hat(omega).to(torch.float64)).to(c2w0.dtype) @ c2w0[:, :3, :3]
+    top = torch.cat([R, (c2w0[:, :3, 3] + tau)[..., None]], -1)
+    last = torch.zeros_like(top[:, :1, :])
+    last[:, 0, 3] = 1.0
+    return torch.cat([top, last], 1)
+
+
+class PoseFitter:
+    """Fits CAMERA POSES (and, with `fit_focal`, focal lengths) to images of a known material: the third inverse use of a trained texture,
+    beside `ParameterFitter` (material parameters) and `TextureFitter` (parameter textures).  Finds where photographs were taken from, or
+    corrects noisy dataset poses.
+
+        fitter = PoseFitter(model, height, width, focal, proxy=AABB(b_0, b_1), n_samples=64, max_rays=4 * 256, lrate=1e-3)
+        c2w, focal, history = fitter.fit(batch, my_loss, init_c2w, n_iters=200)
+
+    An iteration: `compose_poses` (torch), `ray_sampler.posed_rays` (the rays of every image in one launch, from the poses on the device),
+    `DifferentiableRender` on an inputs-only trainer (`trainer_for(model, input_gradients="only", fused=fused)`: dL/d rays_o and dL/d rays_d,
+    no weight gradient), the loss, `backward` -- the trainer's ray gradients, `ntx_generate_rays_posed_adjoint`, torch through the matrix
+    exponential -- and Adam on omega, tau [B,3] (and log f).  Nothing of the pose passes through the host; the host work of an iteration is
+    what `DifferentiableRender` does already.
+    What is differentiated: rays_o and rays_d.  The depths (`t`, the proxy's range), `cone_scale` and the focal's part in them are constants,
+    as everywhere in the trainer's input gradients.  Not taken: IPE models, a coarse + fine pair, instanced scenes, lens distortion."""
+
+    def __init__(self, model, height: int, width: int, focal, proxy=None, near=None, far=None, n_samples: int = 64, max_rays: int = 1024, blur_idx: Optional[int] = None,
+                 perturb: bool = False, raw_noise_std: float = 0, map_exr: bool = False, lrate: float = 1e-3, fit_focal: bool = False, device: int = 0, fused: bool = False,
+                 precision: str = "float32") -> None:
+        """`model`: the trained Nerf-Tex (a Nerf or ParamNerf container; the weights never change); `height`, `width`, `focal` (a float, or
+        one value per image): the cameras' intrinsics, `focal` the start when `fit_focal`; `proxy` (an AABB: `ray_sampler.Proxy`'s rays) or
+        `near` and `far` (`Frustum`'s); `n_samples`, `blur_idx`, `perturb`, `raw_noise_std`, `map_exr`, `fused`, `precision`, `max_rays`: as
+        `ParameterFitter` takes them; `lrate`: Adam's, for omega (radians), tau (scene units) and log f alike."""
+        from .autograd import DifferentiableRender
+        from .train import trainer_for
+        if isinstance(model, dict) or not hasattr(model, "get_blob"):
+            raise TypeError("PoseFitter takes one model (a Nerf or ParamNerf container), not a coarse + fine pair: two passes are two sets of ray gradients")
+        if getattr(model, "pos_encoding", "fourier") == "ipe":
+            raise TypeError("PoseFitter takes a FourierFeatures model: the derivative of the cone gaussians of an IPE model in the rays is not written")
+        if (proxy is None) == (near is None and far is None) or (near is None) != (far is None):
+            raise ValueError("give either proxy (an AABB) or near and far, not both and not neither")
+        self.model, self.height, self.width, self.focal = model, int(height), int(width), focal
+        self.proxy, self.near, self.far = proxy, near, far
+        self.lrate, self.fit_focal, self.device = float(lrate), bool(fit_focal), int(device)
+        self.trainer = trainer_for(model, input_gradients="only", max_rays=int(max_rays), n_samples=int(n_samples), blur_idx=blur_idx, perturb=perturb,
+                                   raw_noise_std=raw_noise_std, map_exr=map_exr, device=device, fused=fused, precision=precision)
+        self.render = DifferentiableRender(self.trainer)
+
+    def rays(self, image_plane_loc, c2w, focal):
+        """`ray_sampler.posed_rays` under the fitter's intrinsics and proxy / frustum."""
+        from .ray_sampler import posed_rays
+        return posed_rays(image_plane_loc, c2w, focal, self.height, self.width, proxy=self.proxy, near=self.near, far=self.far)
+
+    def step(self, batch: dict, loss, c2w, focal, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.), seed: Optional[int] = None):
+        """The loss [1] of `batch` at the poses `c2w` [B,4,4] / [B,3,4] and `focal` [B] (GPU tensors, any torch expression of the caller's
+        leaves), and its `backward()`: the leaves that require grad have their `.grad` (added to what it holds).  `batch`: image_plane_loc
+        [B,R,2], color [B,R,3], alpha [B,R], and parameters [B,P] for a ParamNerf -- one row per image."""
+        import torch
+        if hasattr(loss, "desc"):
+            raise TypeError("PoseFitter takes a callable loss(color_true=, alpha_true=, color_pred=, alpha_pred=) on torch tensors")
+        dev = torch.device("cuda", self.device)
+        to = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32)
+        loc = to(batch["image_plane_loc"])
+        B, R = int(loc.shape[0]), int(loc.shape[1])
+        rays_o, rays_d, t, cone = self.rays(loc, c2w, focal)
+        params = to(batch["parameters"]).reshape(B, -1) if getattr(self.model, "n_params", 0) > 0 else None
+        color, alpha = self.render(rays_o, rays_d, t, params, cone.reshape(-1), composite_bkgd=composite_bkgd, bkgd_color=bkgd_color, seed=seed, rays_per_param_row=R)
+        val = loss(color_true=to(batch["color"]).reshape(B * R, 3), alpha_true=to(batch["alpha"]).reshape(B * R), color_pred=color, alpha_pred=alpha)
+        if not isinstance(val, torch.Tensor) or val.numel() != 1:
+            raise TypeError("the loss must return a scalar tensor")
+        val.reshape(()).backward()
+        return val.detach().reshape(1)
+
+    def fit(self, batches, loss, init_c2w, n_iters: int, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.), callback=None):
+        """`n_iters` Adam steps from the poses `init_c2w` [B,4,4] (or [B,3,4]).  `batches`: one batch dict (every step takes it) or an iterable
+        of them over the SAME images, taken in turn.  Returns (c2w [B,4,4], focal [B], history): GPU tensors and the loss of every step --
+        taken BEFORE its update -- as a list of floats.  `callback(it, c2w, focal)`: called before step `it` with the poses it starts from
+        (detached GPU tensors), to follow a fit; what it does with them -- a copy to the host, say -- is its own cost."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        c2w0 = torch.as_tensor(np.asarray(init_c2w, np.float32) if not isinstance(init_c2w, torch.Tensor) else init_c2w).to(device=dev, dtype=torch.float32)
+        if c2w0.dim() != 3 or tuple(c2w0.shape[1:]) not in ((4, 4), (3, 4)):
+            raise ValueError(f"init_c2w must be [B,4,4] or [B,3,4], got {tuple(c2w0.shape)}")
+        B = int(c2w0.shape[0])
+        omega, tau = (torch.zeros((B, 3), device=dev, requires_grad=True) for _ in range(2))
+        f0 = torch.as_tensor(np.broadcast_to(np.asarray(self.focal, np.float32), (B,)).copy()).to(dev)
+        log_f = torch.log(f0).requires_grad_(self.fit_focal)
+        opt = torch.optim.Adam([omega, tau] + ([log_f] if self.fit_focal else []), lr=self.lrate)
+        up = lambda b: {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(device=dev, dtype=torch.float32).contiguous() for k, v in b.items()
+                        if k in ("image_plane_loc", "color", "alpha", "parameters")}
+        cycle = [up(b) for b in ([batches] if isinstance(batches, dict) else list(batches))]                                # uploaded once
+        focal_now = lambda: torch.exp(log_f) if self.fit_focal else f0
+        history = []
+        for it in range(int(n_iters)):
+            opt.zero_grad(set_to_none=True)
+            c2w = compose_poses(c2w0, omega, tau)
+            if callback is not None:
+                callback(it, c2w.detach(), focal_now().detach())
+            history.append(self.step(cycle[it % len(cycle)], loss, c2w, focal_now(), composite_bkgd=composite_bkgd, bkgd_color=bkgd_color))
+            opt.step()
+        values = torch.cat(history).cpu().tolist() if history else []
+        with torch.no_grad():
+            return compose_poses(c2w0, omega, tau), focal_now().clone(), values
 
 
 # ---- learnable parameter textures: a material parameter that varies over the instancer mesh ---------------------------------------------------

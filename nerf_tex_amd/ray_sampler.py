@@ -73,3 +73,45 @@ class Proxy:
         [n,2] tensor of (row, col) as the reference's pixel samplers return it."""
         return _generate(image_plane_loc, self.height, self.width, self.focal, c2w, 0, self.proxy.b_0,
                          self.proxy.b_1, 0.0, 0.0, device)
+
+
+def posed_rays(image_plane_loc, poses, focal, height: int, width: int, proxy: Any = None, near=None, far=None, rays_per_pose=None):
+    """The rays of a BATCH of cameras whose poses live on the device (`ntx_generate_rays_posed`): `Proxy.__call__` (`proxy`: an AABB) or
+    `Frustum.__call__` (`near`, `far`) for B cameras in one launch on the current stream, without a host round trip for the poses, and
+    differentiable in them -- `poses` [B,4,4] or [B,3,4] (c2w) and `focal` (a float, or a tensor [B]) that require grad receive theirs from
+    dL/d rays_o and dL/d rays_d (`nerf_tex_amd.autograd.PosedRays`, `ntx_generate_rays_posed_adjoint`); t and cone_scale are constants.
+    `image_plane_loc`: [B,R,2] (row, col), or [N,2] with `rays_per_pose` (ray k belongs to pose k // rays_per_pose; the last pose may have
+    fewer).  All tensors on the GPU.  Returns (rays_o [N,3], rays_d [N,3], t [N,2], cone_scale [N,1]); with the same matrix and focal they
+    are `Proxy.__call__`'s / `Frustum.__call__`'s bit for bit."""
+    import torch
+    from .autograd import _posed_rays_function
+    if (proxy is None) == (near is None and far is None) or (near is None) != (far is None):
+        raise ValueError("give either proxy (an AABB: normalised rays_d and the box's t range) or near and far (a frustum), not both and not neither")
+    if not (isinstance(poses, torch.Tensor) and isinstance(image_plane_loc, torch.Tensor) and poses.is_cuda and image_plane_loc.is_cuda):
+        raise ValueError("posed_rays runs on the GPU: poses and image_plane_loc are CUDA(ROCm) tensors")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((4, 4), (3, 4)):
+        raise ValueError(f"poses must be [B,4,4] or [B,3,4], got {tuple(poses.shape)}")
+    B = int(poses.shape[0])
+    loc = image_plane_loc
+    if loc.dim() == 3 and loc.shape[-1] == 2 and rays_per_pose is None:
+        if int(loc.shape[0]) != B:
+            raise ValueError(f"image_plane_loc holds {int(loc.shape[0])} images, poses {B}")
+        rays_per_pose = int(loc.shape[1])
+        loc = loc.reshape(-1, 2)
+    elif loc.dim() != 2 or loc.shape[-1] != 2 or rays_per_pose is None:
+        raise ValueError(f"image_plane_loc must be [B,R,2], or [N,2] with rays_per_pose; got {tuple(loc.shape)}")
+    n, rays_per_pose = int(loc.shape[0]), int(rays_per_pose)
+    if B < 1 or rays_per_pose < 1 or (n > 0 and (n - 1) // rays_per_pose + 1 != B):
+        raise ValueError(f"{n} rays at {rays_per_pose} per pose do not make {B} poses")
+    dev = poses.device
+    if not isinstance(focal, torch.Tensor):
+        focal = torch.full((B,), float(np.float32(focal)), device=dev, dtype=torch.float32)
+    elif focal.dim() == 0:
+        focal = focal.expand(B)
+    if tuple(focal.shape) != (B,) or focal.device != dev or loc.device != dev:
+        raise ValueError(f"focal must be a float or a tensor [B] on the poses' device, got {tuple(focal.shape)} on {focal.device}")
+    mode = 0 if proxy is not None else 1
+    consts = (int(height), int(width), mode, None if proxy is None else tuple(proxy.b_0), None if proxy is None else tuple(proxy.b_1),
+              0.0 if near is None else float(near), 0.0 if far is None else float(far))
+    return _posed_rays_function().apply(poses[:, :3, :].to(torch.float32).contiguous(), focal.to(torch.float32).contiguous(),
+                                        loc.detach().to(torch.float32).contiguous(), rays_per_pose, consts)
