@@ -938,6 +938,53 @@ int ntx_generate_rays_posed_adjoint(const float *poses, const float *focal, int6
                                     int64_t rays_per_pose, int mode, const float *d_rays_o, const float *d_rays_d, float *d_poses, float *d_focal,
                                     void *stream /* hipStream_t */);
 
+/* The distortion loss on the compositing weights (ABI v7, appended; csrc/ntx_ray_losses.hip): the regulariser of mip-NeRF 360 (Barron et
+ * al. 2022, eq. 15), the first loss along the ray that cannot sensibly be written in torch on ntx_trainer_weight_cotangent's hook -- its
+ * textbook form is a double sum over sample pairs, [N][S][S] intermediates.  THE FORMULA, stated here once.  For one ray with weights w_i,
+ * depths z_i (nondecreasing over the live samples) and interval widths delta_i, the sums over the ray's LIVE samples only:
+ *     L       = sum_i sum_j w_i w_j |z_i - z_j|  +  (1/3) sum_i w_i^2 delta_i
+ *     dL/dw_k = 2 sum_j w_j |z_k - z_j|          +  (2/3) w_k delta_k
+ * The depths are constants, as everywhere in the trainers: there is no dL/dz.  Evaluated in O(S): m_i = z_i - z_first, z_first the depth of
+ * the ray's first live sample; with the exclusive prefix sums W_<, M_< of w and w m, and the matching suffix sums W_>, M_>,
+ *     sum_j w_j |z_k - z_j| = (m_k W_<k - M_<k) + (M_>k - m_k W_>k),      L = 2 sum_i w_i (m_i W_<i - M_<i) + (1/3) sum_i w_i^2 delta_i.
+ * The shift by z_first is part of the specification: |z| does not enter the rounding, only the span the ray's samples cover (a float32
+ * restatement against the float64 pair sum, near = 500, span 0.5, S = 256, rel-Linf of loss / gradient: 4.5e-7 / 8.5e-7 shifted, 8.8e-4 /
+ * 1.8e-3 without the shift; tests/test_ray_distortion.py reproduces both).
+ * All pointers DEVICE:
+ *   weights[N,S], z_vals[N,S]   required
+ *   widths[N,S] or NULL         NULL: delta_i = z_{i+1} - z_i, delta_{S-1} = delta_{S-2} (the composite's convention, in ray-parameter units);
+ *                               0 for S == 1, and 0 where the neighbouring depth it is taken from is not finite
+ *   live[N,S] or NULL           a sample is live iff live > 0 (ntx_render_instanced's rule, with dists in that role); NULL: every sample
+ *                               is a candidate.  A sample whose depth is not finite is never live (a ray that missed its proxy: depths
+ *                               inf, weights 0).  A sample that is not live adds nothing and takes gradient exactly 0; its z, w and width
+ *                               are selected away, never multiplied (the sparse instancer leaves those rows unwritten: they may hold NaN)
+ *   ray_scale[N] or NULL (= 1)  a factor per ray on both outputs: the caller's lambda / N / (far - near).  A ray without a live sample has
+ *                               loss 0 and a zero gradient row whatever its ray_scale holds, NaN included
+ *   loss_out[N], grad_out[N,S]  either may be NULL; each is the same bits with or without the other
+ * NTX_E_INVALID, all checked before the launch, so a refused call has written nothing: weights or z_vals NULL; loss_out and grad_out both
+ * NULL; n_samples outside [1, 4096] (the instanced render's limit); n_rays < 0 or >= 2^31; live without widths (differences of neighbouring
+ * depths would read samples that are not live).  n_rays = 0: NTX_OK without a launch.
+ * The kernel: one wave per ray, four rays a workgroup, the sample index across the lanes in chunks of 64 (a coalesced row of 256 bytes).
+ * Pass 1 finds z_first (the first live lane of the first chunk that has one) and the totals of w and w m; pass 2 -- the row comes from L2
+ * the second time -- takes inclusive scans by chunk with carries, the suffix sums as totals less prefix, and the loss from a wave sum.  Pass
+ * 1's totals are added in the order pass 2's carries are, so the last live sample's suffix is exactly 0.  No atomics, no LDS, no scratch;
+ * the order of every sum is fixed by S alone, so a ray's outputs are the same bits in every run, at every n_rays and at every row.
+ * `stream`: a hipStream_t passed as void*, with the meaning of every other entry's `ntx_stream` (NULL = the null stream; the launch is queued
+ * on it and nothing else is touched, waited for or allocated).
+ * Measured on an MI355X (tools/bench_ray_distortion.py, profiles/ray_distortion/bench.json; HIP events, medians of 5 windows of 20 calls, the
+ * sides alternating in one run): loss + gradient 0.017 ms at 1024 x 256 and 0.027 ms at 256 x 1024 with 1 MB of peak memory (the outputs),
+ * beside 0.39 / 0.40 ms and 8 MB for a torch.cumsum statement with autograd and 0.92 / 3.26 ms and 770 / 3075 MB for the pairwise one; a step
+ * of the fused chain at 1024 x 256 takes 7.64 ms under mse, 7.68 ms with this term and 8.55 ms with the pairwise torch term.  The kernel is
+ * bound by launch and memory latency (a call moves 3 MB), not by bandwidth; no speed was promised.  Against the float64 pair sum, rel-Linf
+ * over the batch, error | float32 floor of a sequential restatement (tests/distortion_common.py; the gate is max(4 floors, 5e-7), never
+ * beyond 1e-4): S = 1 .. 3 at most 9.6e-8 | 5.2e-8; S = 63 .. 255 at most 2.6e-7 | 4.8e-7; S = 4096 3.5e-7 | 3.2e-6; near = 500 2.8e-7 |
+ * 8.5e-7; with 35 % of the samples live 3.0e-7 | 3.2e-7; the tightest case (S = 129, saturated rays, given widths) 3.3e-7 | 1.2e-7.
+ * Out of scope: dL/d depths; IPE trainers (they hand out no weights); the fused-loss step (ntx_train_step_gradients with a descriptor: a loss
+ * with this term takes the ntx_train_forward / ntx_train_backward route); coarse + fine pairs; unsorted depths (the O(S) form assumes
+ * nondecreasing live depths: the result is undefined otherwise); second order; any all-reduce. */
+int ntx_ray_distortion(const float *weights, const float *z_vals, const float *widths, const float *live, const float *ray_scale, int64_t n_rays, int n_samples,
+                       float *loss_out, float *grad_out, void *stream /* hipStream_t */);
+
 #ifdef __cplusplus
 }
 #endif

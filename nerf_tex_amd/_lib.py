@@ -183,6 +183,7 @@ SYMBOLS = {
     "ntx_generate_rays_posed": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int, _fp, _fp, C.c_float, C.c_float,
                                           _vp, _vp, _vp, _vp, _vp]),
     "ntx_generate_rays_posed_adjoint": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "ntx_ray_distortion": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
 }
 
 

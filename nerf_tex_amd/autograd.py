@@ -96,9 +96,12 @@ class DifferentiableInstanceRender:
 
 
 def __getattr__(name):
-    """`nerf_tex_amd.autograd.PosedRays`: the torch.autograd.Function of `ray_sampler.posed_rays`, made at its first use."""
+    """`nerf_tex_amd.autograd.PosedRays` / `RayDistortion`: the torch.autograd.Functions of `ray_sampler.posed_rays` and `loss.distortion`, made
+    at their first use."""
     if name == "PosedRays":
         return _posed_rays_function()
+    if name == "RayDistortion":
+        return _ray_distortion_function()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -147,6 +150,34 @@ def _posed_rays_function():
             return (d_poses if ctx.needs_input_grad[0] else None), (d_focal if ctx.needs_input_grad[1] else None), None, None, None
 
     return PosedRays
+
+
+@functools.lru_cache(maxsize=None)
+def _ray_distortion_function():
+    """The torch.autograd.Function behind `loss.distortion`: `ntx_ray_distortion` once in the forward -- one launch writes the per-ray values
+    and their gradient at the weights, which is saved -- and `grad_out[:, None] * saved` in the backward.
+
+        per_ray = RayDistortion.apply(weights [N,S], z_vals [N,S], widths or None, live or None, ray_scale or None)
+
+    Differentiable in `weights` alone (the depths, widths and factors are constants).  First order only: a double backward raises."""
+    import torch
+    from . import loss as _loss
+
+    class RayDistortion(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, weights, z_vals, widths, live, ray_scale):
+            val, grad = _loss.ray_distortion(weights, z_vals, widths, live, ray_scale, with_grad=True)
+            ctx.save_for_backward(grad)
+            ctx.like = weights.dtype
+            return val
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, d_val):
+            (grad,) = ctx.saved_tensors
+            return (d_val.to(grad.dtype)[:, None] * grad).to(ctx.like), None, None, None, None
+
+    return RayDistortion
 
 
 @functools.lru_cache(maxsize=None)

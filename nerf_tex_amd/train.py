@@ -884,13 +884,9 @@ class CoarseFineTrainer:
 
 
 def _loss_keywords(loss) -> set:
-    """The keyword names a callable loss's signature spells out (a loss that takes **kwargs names none: it gets the reference's call)."""
-    import inspect
-    try:
-        params = inspect.signature(loss).parameters.values()
-    except (TypeError, ValueError):
-        return set()
-    return {p.name for p in params if p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)}
+    """`util.loss_keywords`: the keyword names a callable loss's signature spells out."""
+    from . import util
+    return util.loss_keywords(loss)
 
 
 def _is_mip(renderer_config) -> bool:

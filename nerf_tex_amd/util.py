@@ -37,6 +37,16 @@ class EasyDict(dict):
         del self[key]
 
 
+def loss_keywords(loss) -> set:
+    """The keyword names a callable loss's signature spells out (a loss that takes **kwargs names none: it gets the reference's call)."""
+    import inspect
+    try:
+        params = inspect.signature(loss).parameters.values()
+    except (TypeError, ValueError):
+        return set()
+    return {p.name for p in params if p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)}
+
+
 def get_attr_from_path(path: str) -> Any:
     module_name, _, attr_name = path.rpartition(".")
     return getattr(importlib.import_module(module_name), attr_name)
