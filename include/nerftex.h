@@ -985,6 +985,48 @@ int ntx_generate_rays_posed_adjoint(const float *poses, const float *focal, int6
 int ntx_ray_distortion(const float *weights, const float *z_vals, const float *widths, const float *live, const float *ray_scale, int64_t n_rays, int n_samples,
                        float *loss_out, float *grad_out, void *stream /* hipStream_t */);
 
+/* The interlevel loss between two histograms on one ray (ABI v7, appended; csrc/ntx_ray_losses.hip): the partner of the distortion loss in
+ * mip-NeRF 360 (Barron et al. 2022, eq. 13), which supervises a sampler's (proposal) weights with the fine pass's weights, so that the first
+ * network of a coarse + fine pair need not be trained on the image at all.  Its textbook form is an [N][S][S_p] overlap mask.  THE FORMULA,
+ * stated here once.  One ray carries the fine histogram, weights w_i at nondecreasing depths z_i (i < S), and the proposal one, weights ŵ_j
+ * at nondecreasing depths ẑ_j (j < S_p).  A sample's interval is [a_i, b_i]: a_i = z_i; b_i = z_{i+1}, THE NEXT DEPTH ITSELF, for i < S-1;
+ * b_{S-1} = z_{S-1} + (z_{S-1} - z_{S-2}), the composite's last-width convention; b_0 = a_0 when S == 1; the same for the proposal set.  (The
+ * end is the stored neighbour, never z_i + (z_{i+1} - z_i) recomputed: the fine depths are the proposal depths merged with the importance
+ * samples, so exact ties between the two sets are the normal case, and a rounded end would flip an overlap and move the bound by a whole ŵ_j.)
+ *     overlap(i, j)  iff  ẑ_j < b_i  and  b̂_j > a_i           (open intersection: intervals that only touch do not overlap; the counts are the definition)
+ *                    =    j in [lo_i, hi_i),  lo_i = #{j : b̂_j <= a_i},  hi_i = #{j : ẑ_j < b_i}
+ *     bound_i  = sum_{j in [lo_i, hi_i)} ŵ_j                    (added in increasing j)
+ *     r_i      = max(0, w_i - bound_i),     q_i = r_i / (w_i + eps)
+ *     L        = sum_i r_i q_i
+ *     dL/dŵ_j  = -2 sum_{i : overlap(i, j)} q_i                 (added in increasing i; the set is again a contiguous range:
+ *                                                                 i in [#{i : b_i <= ẑ_j}, #{i : a_i < b̂_j}))
+ *     dL/dw_i  = q_i (2 - q_i)
+ * The depths are constants, as everywhere in the trainers: there is no dL/dz.  A ray is LIVE iff every depth of both sets is finite (a ray
+ * that missed its proxy has all depths inf); a ray that is not live has loss 0 and two zero gradient rows whatever its ray_scale and its
+ * weights hold, NaN included: its values are selected away, never multiplied.
+ * All pointers DEVICE:
+ *   weights[N,S], z_vals[N,S], weights_prop[N,S_p], z_prop[N,S_p]   required
+ *   ray_scale[N] or NULL (= 1)     a factor per ray on all three outputs: the caller's lambda / N
+ *   eps                            the guard of the division; Python's default is 2^-23, float32's epsilon (multinerf's choice)
+ *   loss_out[N], grad_prop_out[N,S_p] = dL/dŵ, grad_fine_out[N,S] = dL/dw   any may be NULL; each is the same bits with or without the others
+ * NTX_E_INVALID, all checked before the launch, so a refused call has written nothing: a NULL required pointer; all three outputs NULL;
+ * n_samples or n_prop outside [1, 4096]; n_rays < 0 or >= 2^31; eps not finite or <= 0.  n_rays = 0: NTX_OK without a launch.
+ * The kernel: one wave per ray, four rays a workgroup, a grid-stride over rays.  Pass A puts the fine samples across the lanes in chunks of
+ * 64: each lane finds lo_i and hi_i by binary search over the proposal row, adds ŵ_j over its range DIRECTLY, writes dL/dw_i, keeps q_i in
+ * the wave's own S floats of LDS and accumulates r_i q_i for a wave sum.  Pass B puts the proposal samples across the lanes: the mirrored
+ * searches over the fine row and a direct sum of q_i.  Direct sums, not differences of prefix sums: a prefix difference carries an absolute
+ * error of float32's epsilon times the ray's total weight, and q divides by w + eps -- of order 1 in q where w is about 1e-8, in every ray's
+ * tail; the ranges add up to at most S + S_p over a ray.  The LDS is sized on the host, 16 * S bytes a workgroup (64 KB at the limit); the
+ * searched rows come from the caches.  No atomics, no scratch; every loop index is bounded by the row it reads; the order of every sum is a
+ * function of (S, S_p) and the depths' ranges alone, never of n_rays, the row, the other outputs or the workgroup's other rays, so a ray's
+ * outputs are the same bits in every run.  `stream`: as for ntx_ray_distortion.
+ * Out of scope: dL/d depths; IPE trainers (they hand out no weights); a density-only proposal network (the colour layers still run and take
+ * zeros); shared-network pairs; data-parallel pairs; more than one proposal level; instanced steps; unsorted depths (undefined); second
+ * order. */
+int ntx_ray_interlevel(const float *weights, const float *z_vals, int n_samples, const float *weights_prop, const float *z_prop, int n_prop,
+                       const float *ray_scale, float eps, int64_t n_rays, float *loss_out, float *grad_prop_out, float *grad_fine_out,
+                       void *stream /* hipStream_t */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,7 @@ SYMBOLS = {
                                           _vp, _vp, _vp, _vp, _vp]),
     "ntx_generate_rays_posed_adjoint": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "ntx_ray_distortion": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "ntx_ray_interlevel": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int64, _vp, _vp, _vp, _vp]),
 }
 
 

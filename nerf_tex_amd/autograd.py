@@ -96,12 +96,14 @@ class DifferentiableInstanceRender:
 
 
 def __getattr__(name):
-    """`nerf_tex_amd.autograd.PosedRays` / `RayDistortion`: the torch.autograd.Functions of `ray_sampler.posed_rays` and `loss.distortion`, made
-    at their first use."""
+    """`nerf_tex_amd.autograd.PosedRays` / `RayDistortion` / `RayInterlevel`: the torch.autograd.Functions of `ray_sampler.posed_rays`,
+    `loss.distortion` and `loss.interlevel`, made at their first use."""
     if name == "PosedRays":
         return _posed_rays_function()
     if name == "RayDistortion":
         return _ray_distortion_function()
+    if name == "RayInterlevel":
+        return _ray_interlevel_function()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -178,6 +180,38 @@ def _ray_distortion_function():
             return (d_val.to(grad.dtype)[:, None] * grad).to(ctx.like), None, None, None, None
 
     return RayDistortion
+
+
+@functools.lru_cache(maxsize=None)
+def _ray_interlevel_function():
+    """The torch.autograd.Function behind `loss.interlevel`: `ntx_ray_interlevel` once in the forward -- one launch writes the per-ray values
+    and their gradients at both sets of weights, which are saved -- and `grad_out[:, None] * saved` in the backward, for whichever of the two
+    requires grad.
+
+        per_ray = RayInterlevel.apply(weights [N,S], z_vals [N,S], weights_prop [N,S_p], z_prop [N,S_p], ray_scale or None, eps)
+
+    Differentiable in `weights_prop` and `weights` (the depths and factors are constants).  First order only: a double backward raises."""
+    import torch
+    from . import loss as _loss
+
+    class RayInterlevel(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, weights, z_vals, weights_prop, z_prop, ray_scale, eps):
+            val, grad_prop, grad_fine = _loss.ray_interlevel(weights, z_vals, weights_prop, z_prop, ray_scale, eps, with_grad=True)
+            ctx.save_for_backward(grad_prop, grad_fine)
+            ctx.like = (weights.dtype, weights_prop.dtype)
+            return val
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, d_val):
+            grad_prop, grad_fine = ctx.saved_tensors
+            d = d_val.to(grad_prop.dtype)[:, None]
+            d_fine = (d * grad_fine).to(ctx.like[0]) if ctx.needs_input_grad[0] else None
+            d_prop = (d * grad_prop).to(ctx.like[1]) if ctx.needs_input_grad[2] else None
+            return d_fine, None, d_prop, None, None, None
+
+    return RayInterlevel
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,7 @@
 // ntx_ray_losses.hip -- losses along a ray on the compositing weights: ntx_ray_distortion, the distortion regulariser of mip-NeRF 360 in its
-// O(S) form and its gradient at the weights (the formula: include/nerftex.h, at the entry).  One unit of its own: no context, no trainer, no
-// header of the render or training kernels.  gfx950 only.  -ffp-contract=off: nothing below is fused.
+// O(S) form and its gradient at the weights, and ntx_ray_interlevel, the interlevel (proposal) loss of the same paper between a fine and a
+// proposal histogram and its gradients at both sets of weights (the formulas: include/nerftex.h, at the entries).  One unit of its own: no
+// context, no trainer, no header of the render or training kernels.  gfx950 only.  -ffp-contract=off: nothing below is fused.
 #include "ntx_entry.h"
 
 namespace {
@@ -96,6 +97,90 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void ray_distortion_kernel(Dis
         }
     }
 }
+// ---- the interlevel loss (include/nerftex.h at ntx_ray_interlevel has the formula) ----------------------------------------------------------
+struct InterlevelArgs {
+    const float *w, *z, *wp, *zp, *ray_scale;         // [N][S], [N][S], [N][Sp], [N][Sp], NULL or [N]
+    float *loss, *grad_prop, *grad_fine;              // NULL or [N], NULL or [N][Sp], NULL or [N][S]
+    long long n_rays; int S, Sp; float eps;
+};
+
+// the end of interval k of a row of n depths: the next depth ITSELF, and the last width repeated behind the last one (k < n)
+__device__ __forceinline__ float interval_end(const float *row, int k, int n) {
+    if (k + 1 < n) return row[k + 1];
+    const float zl = row[k];
+    return n > 1 ? zl + (zl - row[k - 1]) : zl;
+}
+// #{k < n : end_k <= x} and #{k < n : row_k < x}: both predicates are monotone in k (the row is nondecreasing), at most 13 steps each
+__device__ __forceinline__ int count_ends_le(const float *row, int n, float x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (interval_end(row, mid, n) <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int count_starts_lt(const float *row, int n, float x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// A wave per ray; q of the ray's fine samples passes from pass A to pass B through the wave's own S floats of LDS (sized on the host:
+// RAYS_PER_BLOCK * S * 4 bytes, 64 KB at the limit).  The searched rows come from L1 / L2.
+__global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void ray_interlevel_kernel(InterlevelArgs a) {
+    extern __shared__ float q_lds[];
+    const int lane = threadIdx.x & 63, S = a.S, Sp = a.Sp;
+    float *q_row = q_lds + (size_t)(threadIdx.x >> 6) * S;
+    for (long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6); ray < a.n_rays; ray += (long long)gridDim.x * RAYS_PER_BLOCK) {
+        const float *z = a.z + (size_t)ray * S, *w = a.w + (size_t)ray * S;
+        const float *zp = a.zp + (size_t)ray * Sp, *wp = a.wp + (size_t)ray * Sp;
+        // live iff every depth of both sets is finite
+        bool bad = false;
+        for (int s = lane; s < S; s += 64) bad |= !__builtin_isfinite(z[s]);
+        for (int s = lane; s < Sp; s += 64) bad |= !__builtin_isfinite(zp[s]);
+        if (__ballot(bad) != 0) {                           // (wave-uniform) 0 and two zero rows, whatever ray_scale and the weights hold
+            if (a.loss && lane == 0) a.loss[ray] = 0.0f;
+            if (a.grad_fine) for (int s = lane; s < S; s += 64) a.grad_fine[(size_t)ray * S + s] = 0.0f;
+            if (a.grad_prop) for (int s = lane; s < Sp; s += 64) a.grad_prop[(size_t)ray * Sp + s] = 0.0f;
+            continue;
+        }
+        const float scale = a.ray_scale ? a.ray_scale[ray] : 1.0f;
+        // pass A: fine samples across the lanes; the proposal weights a sample's interval overlaps, added directly in increasing j
+        float acc = 0.0f;
+        for (int i = lane; i < S; i += 64) {
+            const float ai = z[i], bi = interval_end(z, i, S), wi = w[i];
+            const int lo = count_ends_le(zp, Sp, ai), hi = count_starts_lt(zp, Sp, bi);   // 0 <= lo, hi <= Sp
+            float bound = 0.0f;
+            for (int j = lo; j < hi; ++j) bound += wp[j];
+            const float d = wi - bound, r = d > 0.0f ? d : 0.0f, q = r / (wi + a.eps);
+            acc += r * q;
+            q_row[i] = q;
+            if (a.grad_fine) a.grad_fine[(size_t)ray * S + i] = scale * (q * (2.0f - q));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // q_row: written and read by this wave alone
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // pass B: proposal samples across the lanes; q of the fine samples an interval overlaps, added directly in increasing i
+        if (a.grad_prop) {
+            for (int j = lane; j < Sp; j += 64) {
+                const float aj = zp[j], bj = interval_end(zp, j, Sp);
+                const int lo = count_ends_le(z, S, aj), hi = count_starts_lt(z, S, bj);   // 0 <= lo, hi <= S
+                float sum = 0.0f;
+                for (int i = lo; i < hi; ++i) sum += q_row[i];
+                a.grad_prop[(size_t)ray * Sp + j] = scale * (0.0f - 2.0f * sum);
+            }
+        }
+        if (a.loss) {
+            const float L = wave_sum(acc);
+            if (lane == 0) a.loss[ray] = scale * L;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the next ray of this wave writes q_row again
+        __builtin_amdgcn_wave_barrier();
+    }
+}
 }  // namespace
 
 extern "C" int ntx_ray_distortion(const float *weights, const float *z_vals, const float *widths, const float *live, const float *ray_scale, int64_t n_rays, int n_samples,
@@ -113,6 +198,27 @@ extern "C" int ntx_ray_distortion(const float *weights, const float *z_vals, con
     int64_t nb = (n_rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
     if (nb > 256 * 8) nb = 256 * 8;   // 8 workgroups per CU, grid-stride over rays
     ray_distortion_kernel<<<dim3((unsigned)nb), dim3(64 * RAYS_PER_BLOCK), 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return NTX_OK;
+}
+
+extern "C" int ntx_ray_interlevel(const float *weights, const float *z_vals, int n_samples, const float *weights_prop, const float *z_prop, int n_prop,
+                                  const float *ray_scale, float eps, int64_t n_rays, float *loss_out, float *grad_prop_out, float *grad_fine_out, void *stream) {
+    if (!weights || !z_vals || !weights_prop || !z_prop) return ntx_set_error(NTX_E_INVALID, "weights, z_vals, weights_prop or z_prop is NULL");
+    if (!loss_out && !grad_prop_out && !grad_fine_out) return ntx_set_error(NTX_E_INVALID, "loss_out, grad_prop_out and grad_fine_out are all NULL");
+    if (n_samples < 1 || n_samples > 4096) return ntx_set_error(NTX_E_INVALID, "n_samples %d outside [1, 4096]", n_samples);
+    if (n_prop < 1 || n_prop > 4096) return ntx_set_error(NTX_E_INVALID, "n_prop %d outside [1, 4096]", n_prop);
+    if (n_rays < 0 || n_rays > 0x7fffffff) return ntx_set_error(NTX_E_INVALID, "n_rays %lld outside [0, 2^31)", (long long)n_rays);
+    if (!(eps > 0.0f) || !__builtin_isfinite(eps)) return ntx_set_error(NTX_E_INVALID, "eps must be finite and > 0");
+    if (n_rays == 0) return NTX_OK;
+    InterlevelArgs a{};
+    a.w = weights; a.z = z_vals; a.wp = weights_prop; a.zp = z_prop; a.ray_scale = ray_scale;
+    a.loss = loss_out; a.grad_prop = grad_prop_out; a.grad_fine = grad_fine_out;
+    a.n_rays = n_rays; a.S = n_samples; a.Sp = n_prop; a.eps = eps;
+    int64_t nb = (n_rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
+    if (nb > 256 * 8) nb = 256 * 8;   // grid-stride over rays
+    const size_t lds = (size_t)RAYS_PER_BLOCK * (size_t)n_samples * sizeof(float);   // q of four rays: 64 KB at S = 4096, two workgroups a CU
+    ray_interlevel_kernel<<<dim3((unsigned)nb), dim3(64 * RAYS_PER_BLOCK), lds, (hipStream_t)stream>>>(a);
     HIP_TRY(hipGetLastError());
     return NTX_OK;
 }

@@ -11,7 +11,9 @@ class by module path) and run the step as `ntx_train_forward`, the loss and its 
 (`nerf_tex_amd.autograd` is the same as a differentiable op).  A callable whose signature also names `weights` (and `z_vals`) is a loss ALONG
 the ray: it receives the compositing weights [N, S] (and the step's depths) and its gradient at the weights goes back through
 `ntx_trainer_weight_cotangent`; `expected_depth` below is the helper such a loss starts from, and `Distortion` wraps any loss with the
-distortion regulariser of mip-NeRF 360 on those weights (`ntx_ray_distortion`: the formula is stated at the entry in include/nerftex.h)."""
+distortion regulariser of mip-NeRF 360 on those weights (`ntx_ray_distortion`: the formula is stated at the entry in include/nerftex.h).
+`ray_interlevel` / `interlevel` are the same paper's interlevel loss between the weights of two passes (`ntx_ray_interlevel`, stated at its
+entry too): the loss `train.ProposalTrainer` trains a sampler's network with; `Interlevel` is the config key that asks for it."""
 
 from __future__ import annotations
 
@@ -130,6 +132,47 @@ def distortion(weights, z_vals, widths=None, live=None, ray_scale=None):
     sample has no depth and is not part of the sum."""
     from . import autograd
     return autograd.RayDistortion.apply(weights, z_vals, widths, live, ray_scale)
+
+
+def ray_interlevel(weights, z_vals, weights_prop, z_prop, ray_scale=None, eps: float = 2.0 ** -23, with_grad: bool = False):
+    """`ntx_ray_interlevel` on device tensors, on the current stream: the interlevel loss of every ray (include/nerftex.h has the formula, the
+    liveness rule and the limits) between the fine histogram -- weights [N, S] at depths z_vals [N, S] -- and the proposal one -- weights_prop
+    [N, S_p] at z_prop [N, S_p] -- with an optional per-ray factor ray_scale [N].  Returns loss [N], or (loss [N], grad_prop [N, S_p] = d loss /
+    d weights_prop, grad_fine [N, S] = d loss / d weights) with `with_grad`.  Nothing here is in the autograd graph: `interlevel` is."""
+    import torch
+    (w, z, _, _, ray_scale), n, S = _ray_tensors(weights, z_vals, None, None, ray_scale)
+    if not isinstance(weights_prop, torch.Tensor) or weights_prop.dim() != 2 or int(weights_prop.shape[0]) != n:
+        raise ValueError(f"weights_prop: a [N, S_p] tensor with the weights' {n} rays")
+    (wp, zp, _, _, _), _, Sp = _ray_tensors(weights_prop, z_prop, None, None, None)
+    if wp.device != w.device:
+        raise ValueError("weights and weights_prop live on different devices")
+    loss = torch.empty((n,), device=w.device, dtype=torch.float32)
+    grad_prop = torch.empty((n, Sp), device=w.device, dtype=torch.float32) if with_grad else None
+    grad_fine = torch.empty((n, S), device=w.device, dtype=torch.float32) if with_grad else None
+    ptr = lambda x: None if x is None else x.data_ptr()
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.lib.ntx_ray_interlevel(ptr(w), ptr(z), S, ptr(wp), ptr(zp), Sp, ptr(ray_scale), float(eps), n, ptr(loss), ptr(grad_prop), ptr(grad_fine),
+                                               torch.cuda.current_stream(w.device).cuda_stream))
+    return (loss, grad_prop, grad_fine) if with_grad else loss
+
+
+def interlevel(weights, z_vals, weights_prop, z_prop, ray_scale=None, eps: float = 2.0 ** -23):
+    """`ray_interlevel` as a differentiable op (`nerf_tex_amd.autograd.RayInterlevel`): per-ray values [N], differentiable in `weights_prop` and
+    in `weights`, for whichever requires grad (the depths are constants), first order only.  The mip-NeRF 360 use detaches the fine weights:
+    `interlevel(weights.detach(), z_all, weights_prop, z_prop).mean()` trains the sampler alone."""
+    from . import autograd
+    return autograd.RayInterlevel.apply(weights, z_vals, weights_prop, z_prop, ray_scale, float(eps))
+
+
+class Interlevel:
+    """The `sampler_loss` block of a training config: {'module': 'nerf_tex_amd.loss.Interlevel', 'weight': 1.0} makes `Trainer.from_config`
+    build a `train.ProposalTrainer`, whose first network learns from `weight` * mean_n(interlevel_n) alone.  It holds the two numbers; the
+    trainer calls `ray_interlevel`."""
+
+    def __init__(self, weight: float = 1.0, eps: float = 2.0 ** -23) -> None:
+        self.weight, self.eps = float(weight), float(eps)
+        if not self.eps > 0:
+            raise ValueError("eps must be > 0")
 
 
 class Distortion:

@@ -99,7 +99,10 @@ class Trainer:
     def from_config(cls, config: dict, max_rays: Optional[int] = None, device: int = 0, weights=None):
         """The trainer and the loss a reference TRAINING config asks for, from its own blocks as written (train.py:20-52): `model_config`
         (network.model.ParamNerf ...), `loss_config`, `lrate`, `lrate_decay`, `renderer_config` (n_samples, perturb, raw_noise_std, blur_idx,
-        map_exr; render_chunk / net_chunk / downsampling_factor have no meaning here: a step is one batch).  `max_rays` defaults to the config's batch --
+        map_exr; render_chunk / net_chunk / downsampling_factor have no meaning here: a step is one batch), and this package's own top-level
+        keys `precision`, `sampler_loss` ({'module': 'nerf_tex_amd.loss.Interlevel', 'weight': 1.0}: a `ProposalTrainer` instead of a
+        `CoarseFineTrainer`; it needs a CoarseFine model block and n_importance > 0) and `proposal_model_config` (with `sampler_loss`: a block
+        that replaces the first network's with a smaller one).  `max_rays` defaults to the config's batch --
         `train_dataset_config.batchsize` images x `pixel_sampler_config.n_samples` rays -- when the config says it.  Returns (trainer, loss).
         The data side (`nerf_tex_amd.dataset`) and the loop around the step are `Train`'s."""
         from . import util
@@ -128,6 +131,16 @@ class Trainer:
             raise NotImplementedError("Importance sampling for mip-NeRF style rendering is not implemented in the reference either (renderer.py:403-404)")
         if mip != (getattr(model, "pos_encoding", "fourier") == "ipe"):             # the render side's pairing (renderer.py:71, :338)
             raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "IPE models train under MipRenderer, FourierFeatures models under Renderer")
+        sampler = cfg.get("sampler_loss")                                        # a top-level key of the config: the proposal pair
+        if sampler is not None:
+            sampler = util.instantiate(dict(sampler))
+            fine = models.get(model.name + "_fine")
+            if not hasattr(sampler, "weight") or fine is None or n_importance < 1:
+                raise ValueError("sampler_loss (nerf_tex_amd.loss.Interlevel) needs a CoarseFine model block and n_importance > 0")
+            if cfg.get("proposal_model_config") is not None:                       # a smaller first network, under the first network's name
+                made = util.instantiate(dict(cfg["proposal_model_config"], name=model.name))
+                model = made[model.name] if isinstance(made, dict) else made
+            return ProposalTrainer(model, fine, n_importance=n_importance, interlevel_weight=sampler.weight, interlevel_eps=sampler.eps, **kw), loss
         if n_importance > 0:                                                    # renderer.py:125-138: a coarse and a fine pass
             return CoarseFineTrainer(model, models.get(model.name + "_fine"), n_importance=n_importance, **kw), loss
         return (trainer_for if cls is Trainer else cls)(model, **kw), loss      # the chain where it takes the model, layer by layer otherwise
@@ -881,6 +894,80 @@ class CoarseFineTrainer:
                                                 flat("color", 3), alpha, loss, composite_bkgd=composite_bkgd, bkgd_color=bkgd_color, seed=seed, rays_per_param_row=R)
         self.apply_gradients()
         return {"loss": val, "color_pred": c.reshape(B, R, 3), "alpha_pred": a.reshape(B, R), "color_pred_coarse": cc.reshape(B, R, 3), "alpha_pred_coarse": ac.reshape(B, R)}
+
+
+class ProposalTrainer(CoarseFineTrainer):
+    """A proposal network and a fine network under the interlevel loss of mip-NeRF 360 (`ntx_ray_interlevel`: the formula is stated at the
+    entry in include/nerftex.h): the first network only places the fine pass's samples, and learns from the fine pass's weights alone --
+    it is never asked for a colour, so it may be much smaller than the fine one.  A step: `proposal.forward(return_weights=True)` on the
+    depths the step would place itself; `ntx_sample_pdf` on its weights (the `u`, seed and perturb rule of `CoarseFineTrainer`); the fine
+    network's whole step on the merged depths under the caller's loss (a descriptor object or any callable the fine trainer takes);
+    `ray_interlevel(w_fine, z_all, w_prop, z_prop, ray_scale=interlevel_weight / N)` -- N counts every ray of the batch, missed ones
+    too; `proposal.backward(zeros, None, d_weights=grad_prop)`.  The image loss never reaches the proposal network (its colour layers take
+    exact zeros) and the interlevel term never reaches the fine one.  Always two networks, each through `trainer_for` (their architectures
+    may differ); an IPE model hands out no weights (NTX_E_UNSUPPORTED).  Everything else -- `apply_gradients`, `save` / `restore`,
+    `hand_weights_to_models`, `step`, `train_step` -- is the parent's.  Out of scope: shared-network and data-parallel pairs, more than one
+    proposal level, instanced steps, `input_gradients=`."""
+
+    def __init__(self, proposal_model, model, max_rays: int = 1024, n_samples: int = 64, n_importance: int = 64, interlevel_weight: float = 1.0,
+                 interlevel_eps: float = 2.0 ** -23, **kw) -> None:
+        if model is None or model is proposal_model:
+            raise ValueError("ProposalTrainer holds two networks: a proposal model and a fine model of its own (a shared network has nothing to propose to)")
+        for m in (proposal_model, model):
+            if getattr(m, "pos_encoding", "fourier") == "ipe":
+                raise _lib.NtxError(_lib.NTX_E_UNSUPPORTED, "an IPE trainer hands out no composite weights, so the interlevel loss has nothing to compare")
+        super().__init__(proposal_model, model, max_rays=max_rays, n_samples=n_samples, n_importance=n_importance, **kw)
+        self.interlevel_weight, self.interlevel_eps = float(interlevel_weight), float(interlevel_eps)
+        self.last_interlevel = None
+
+    proposal = property(lambda self: self.coarse)
+
+    def gradients_step(self, rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, loss, composite_bkgd: bool = False, bkgd_color=(1., 1., 1.),
+                       seed: Optional[int] = None, rays_per_param_row: int = 1, u=None, on_coarse=None):
+        """Both networks' gradients.  Returns (loss [1] = fine loss + interlevel_weight * mean interlevel, color_pred, alpha_pred,
+        color_pred_prop, alpha_pred_prop); `last_interlevel` [1] holds the interlevel term alone, `last_z` the merged depths.  `u`, `seed`,
+        `on_coarse`: as in `CoarseFineTrainer.gradients_step` (`on_coarse()` runs after the proposal's forward)."""
+        import torch
+        from . import loss as _loss
+        dev = torch.device("cuda", self.device)
+        to = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(device=dev, dtype=torch.float32).contiguous()
+        rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true = (to(a) for a in (rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true))
+        n, S, NI = rays_o.reshape(-1, 3).shape[0], self.n_samples, self.n_importance
+        if seed is None:
+            seed = self._calls
+        self._calls += 1
+        step = dict(composite_bkgd=composite_bkgd, bkgd_color=bkgd_color, seed=seed, rays_per_param_row=rays_per_param_row)
+        z_prop = self.coarse._sample_depths(t, seed, S)                        # the depths the forward would place itself
+        cp, ap, w_prop = self.coarse.forward(rays_o, rays_d, t, parameters, cone_scale, z_vals=z_prop, n_samples=S, return_weights=True, **step)
+        if on_coarse is not None:
+            on_coarse()
+        if not self.perturb and u is None:
+            u = torch.rand((n, NI), device=dev, generator=torch.Generator(device=dev).manual_seed(int(seed) & (2 ** 63 - 1)))
+        u = None if self.perturb else to(u).reshape(n, NI).contiguous()
+        z_all = torch.empty((n, S + NI), device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.ntx_sample_pdf(t.data_ptr(), None, w_prop.data_ptr(), u.data_ptr() if u is not None else None, n, S, NI,
+                                               _lib.FLAG_PERTURB if self.perturb else 0, int(seed) & (2 ** 64 - 1), None, z_all.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream))
+        fine_step = lambda fn: self.fine.gradients_step(rays_o, rays_d, t, parameters, cone_scale, color_true, alpha_true, fn, z_vals=z_all, n_samples=S + NI, **step)
+        if hasattr(loss, "desc"):                                              # the fused-loss step leaves its weights where they are registered
+            w_fine = torch.empty((n, S + NI), device=dev)
+            with self.fine._weights_into(w_fine):
+                val_f, cf, af = fine_step(loss)
+        else:                                                                  # a callable: the fine trainer's forward hands the weights to a loss that names them
+            names, seen = _loss_keywords(loss), {}
+
+            def along(color_true=None, alpha_true=None, color_pred=None, alpha_pred=None, weights=None, z_vals=None):
+                seen["weights"] = weights.detach()
+                more = {k: v for k, v in (("weights", weights), ("z_vals", z_vals)) if k in names}
+                return loss(color_true=color_true, alpha_true=alpha_true, color_pred=color_pred, alpha_pred=alpha_pred, **more)
+            val_f, cf, af = fine_step(along)
+            w_fine = seen["weights"]
+        scale = torch.full((n,), self.interlevel_weight / n, device=dev)
+        per_ray, grad_prop, _ = _loss.ray_interlevel(w_fine, z_all, w_prop, z_prop, ray_scale=scale, eps=self.interlevel_eps, with_grad=True)
+        self.coarse.backward(torch.zeros_like(cp), None, d_weights=grad_prop)
+        self.last_interlevel, self.last_z = per_ray.sum().reshape(1), z_all
+        return val_f + self.last_interlevel, cf, af, cp, ap
 
 
 def _loss_keywords(loss) -> set:
