@@ -6,7 +6,10 @@ shift by the first live depth (what any float32 evaluation of that form is off b
 THE GATE, everywhere: error <= max(4 floors, 5e-7), and never beyond 1e-4; errors and floors are rel-Linf over the batch, max|x - ref| /
 max|ref|.  Four float32 floors is the project's standing convention; 5e-7 is 4 ulp of float32, for the tiny cases whose
 floor is a single rounding; 1e-4 is the house bar and the cap.  tests/test_ray_distortion.py holds every floor <= 2.5e-5, so four floors
-never reach the cap."""
+never reach the cap.
+
+Appended for the calls past the capped grid and the liveness an instanced step produces: `PATCH_PATTERNS`, `live_limit_case`, `large_base` /
+`cycled` / `large_scale` / `large_reference` (the float64 reference is computed on the 257 base rows alone and cycled)."""
 
 import functools
 
@@ -135,6 +138,7 @@ def parity_cases():
     rows.append(("S65_N9_smooth", 9, 65, "smooth", NEAR, SPAN, None))
     rows.append(("S129_N3_peaky_widths", 3, 129, "peaky", NEAR, SPAN, "given"))
     rows.append(("S256_N5_near500", 5, 256, "smooth", (500.0, 500.0), (0.5, 0.5), None))
+    rows.append(("S65_N257_smooth", 257, 65, "smooth", NEAR, SPAN, None))          # the base of the calls past the capped grid (`large_base`)
     return rows
 
 
@@ -197,6 +201,10 @@ def held(got_loss, got_grad, want, floors, label, report=print):
 # ---- liveness ----------------------------------------------------------------------------------------------------------------------------
 LIVE_N, LIVE_S = 5, 200                      # four chunks, the last one short
 LIVE_PATTERNS = ["all_dead", "one_in_last_chunk", "first_behind_chunk0", "random35"]
+# ... and as the patches of an instanced step leave a ray (seeded by the list index: append only): a whole dead chunk BETWEEN live ones (pass 2's
+# empty-chunk branch entered with carries that are not zero), whole dead chunks BEHIND the last live sample, patches that end on the chunk edges
+PATCH_PATTERNS = ["dead_chunk_between", "dead_tail", "patch_ends_on_chunk_edges", "two_short_patches"]
+LIVE_PATTERNS += PATCH_PATTERNS
 
 
 @functools.lru_cache(maxsize=None)
@@ -215,11 +223,96 @@ def live_case(pattern):
         mask[:, 150] = True
     elif pattern == "random35":
         mask = rng.uniform(size=(n, S)) < 0.35
+    elif pattern == "dead_chunk_between":                                         # two patches, chunk [64, 128) entirely dead between them
+        mask[:, :64] = rng.uniform(size=(n, 64)) < 0.6
+        mask[:, 128:] = rng.uniform(size=(n, S - 128)) < 0.6
+        mask[:, [5, 190]] = True
+    elif pattern == "dead_tail":                                                  # the ray leaves its patch early: nothing behind sample 70
+        mask[:, :70] = rng.uniform(size=(n, 70)) < 0.7
+        mask[:, [3, 69]] = True
+    elif pattern == "patch_ends_on_chunk_edges":
+        mask[:, 37:64] = True
+        mask[:, 128:192] = True
+    elif pattern == "two_short_patches":
+        mask[:, 10:14] = True
+        mask[:, 150:153] = True
+    return _live_pack(w, z, widths, mask, rng)
+
+
+def _live_pack(w, z, widths, mask, rng):
+    n, S = mask.shape
     live = np.where(mask, widths, F(0)).astype(F)                                 # dists in the role of live: > 0 inside a patch
     live[~mask & (rng.uniform(size=(n, S)) < 0.3)] = F(-1.0)
     w, z, widths = (np.where(mask, a, F(np.nan)).astype(F) for a in (w, z, widths))
     scale = rng.uniform(0.5, 2.0, size=n).astype(F)
     return w, z, widths, live, scale, mask
+
+
+LIMIT_N, LIMIT_S, LIMIT_LIVE = 3, 4096, ((100, 1000), (3000, 4090))                # 31 whole dead chunks, 1024 .. 3007, between live ones
+LIMIT_SEED = 91                                                                  # (of the weights: the one to change if a floor passes FLOOR_GUARD)
+
+
+@functools.lru_cache(maxsize=None)
+def live_limit_case():
+    """`live_case`'s tuple at the sample limit: 3 rays of 4096 samples, live exactly in [100, 1000) and [3000, 4090)."""
+    n, S = LIMIT_N, LIMIT_S
+    w, z = ray_batch(n, S, "smooth", NEAR, SPAN, seed=LIMIT_SEED)
+    rng = np.random.default_rng(LIMIT_SEED + 1)
+    widths = (default_widths(z) * rng.uniform(0.8, 1.6, size=(n, 1)).astype(F)).astype(F)
+    mask = np.zeros((n, S), bool)
+    for a, b in LIMIT_LIVE:
+        mask[:, a:b] = True
+    return _live_pack(w, z, widths, mask, rng)
+
+
+@functools.lru_cache(maxsize=None)
+def live_figures(pattern):
+    """(float64 reference, float32 floors) of `live_case(pattern)` -- "limit": of `live_limit_case()` --, computed once."""
+    w, z, widths, live, scale, _ = live_limit_case() if pattern == "limit" else live_case(pattern)
+    want, f32 = pairwise64(w, z, widths, live, scale), linear_form(w, z, widths, live, scale)
+    return want, (rel_linf(f32[0], want[0]), rel_linf(f32[1], want[1]))
+
+
+# ---- past the capped grid: 256 * 8 workgroups of four waves, a ray a wave; from 8193 rays on a wave takes a second ray ---------------------
+GRID_RAYS = 256 * 8 * 4
+LARGE_N = [GRID_RAYS, GRID_RAYS + 1, 2 * GRID_RAYS + 5]      # one pass exactly; one wave's second ray; three passes for five waves
+LARGE_BASE = "S65_N257_smooth"                               # 257 is prime and 8192 mod 257 = 225: a wave meets another base row in every pass
+MISSED, PARTIAL, NAN_W = 0, 1, 130                           # the replaced rows of the base; MISSED and NAN_W have no live sample
+PARTIAL_LIVE = 30
+
+
+@functools.lru_cache(maxsize=None)
+def large_base():
+    """(w, z, dead [257], (loss, grad) float64 without a ray_scale, floors) of the base batch: the case's rays with three rows replaced -- a
+    missed ray (depths inf, weights 0), a ray finite only in its first 30 samples, a ray with NaN weights behind depths that are not finite."""
+    case = [c for c in CASES if c[0] == LARGE_BASE][0]
+    w, z, widths, _ = case_inputs(case)
+    assert widths is None
+    w, z = w.copy(), z.copy()
+    w[MISSED], z[MISSED] = 0.0, np.inf
+    z[PARTIAL, PARTIAL_LIVE:] = np.inf
+    w[NAN_W], z[NAN_W, ::2], z[NAN_W, 1::2] = np.nan, np.inf, np.nan
+    dead = ~np.isfinite(z).any(1)
+    return w, z, dead, pairwise64(w, z), floor(case)
+
+
+def cycled(a, n):
+    """Row k of the result is row k mod len(a) of a."""
+    return np.asarray(a)[np.arange(n) % len(a)]
+
+
+def large_scale(n, dead, seed=5):
+    """A per-ray ray_scale over the whole large batch, NaN on the rays without a live sample."""
+    scale = np.random.default_rng(seed + n).uniform(0.5, 2.0, size=n).astype(F)
+    scale[cycled(dead, n)] = np.nan
+    return scale
+
+
+def large_reference(n, scale):
+    """The float64 reference of the 257 base rows, cycled, times `scale`; zeros on the dead rows whatever `scale` holds there."""
+    _, _, dead, (loss, grad), _ = large_base()
+    s = np.where(cycled(dead, n), 0.0, np.nan_to_num(np.asarray(scale, np.float64), nan=0.0))
+    return cycled(loss, n) * s, cycled(grad, n) * s[:, None]
 
 
 # ---- the loss a trainer takes, stated with the pair sum in torch ---------------------------------------------------------------------------

@@ -9,7 +9,9 @@ case: a case whose loss is all zeros would pass any gate.
 
 Inputs: `ray_batch` rays for the proposal set; the fine depths are those merged with uniform draws inside the span and sorted (exact ties
 between the two sets everywhere; where a case has no more fine than proposal samples, a sorted subset of the proposal depths), or -- "free"
--- independent depths with no ties; the fine weights are the composite's weights of an independent density."""
+-- independent depths with no ties; the fine weights are the composite's weights of an independent density.  Off the merged grid
+(`off_grid_inputs`): "repeats", exact repeats inside either set, and "beyond", fine samples far outside the proposal's range.  `large_base` /
+`large_reference`: the 257 rows the calls past the capped grid cycle, and their float64 reference."""
 
 import functools
 
@@ -72,7 +74,7 @@ def dense_torch(w, z, wp, zp, eps=EPS):
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
 NEAR, SPAN = (2.0, 6.0), (0.5, 2.0)
-# (id, N, S_p, S, family, near, span, depths: "merged" | "free")
+# (id, N, S_p, S, family, near, span, depths: "merged" | "free" | "repeats" | "beyond")
 # (S_p, S, N, family): N is no multiple of the four rays of a workgroup; two proposal samples of a smooth ray cover whatever the fine
 # pass holds (max q 0.06), so that shape is peaky
 _SHAPES = [(1, 1, 5, "smooth"), (1, 2, 3, "peaky"), (2, 3, 5, "peaky"), (3, 2, 9, "smooth"), (8, 16, 9, "smooth"), (63, 64, 5, "peaky"), (64, 65, 257, "smooth"),
@@ -86,7 +88,12 @@ def parity_cases():
     rows.append(("P65_S129_N5_smooth", 5, 65, 129, "smooth", NEAR, SPAN, "merged"))
     rows.append(("P64_S128_N5_near500", 5, 64, 128, "smooth", (500.0, 500.0), (0.5, 0.5), "merged"))
     rows.append(("P63_S130_N6_free", 6, 63, 130, "peaky", NEAR, SPAN, "free"))
+    for how in OFF_GRID:                                # inputs off the merged grid: `off_grid_inputs`
+        rows += [(f"P65_S130_N6_{how}_{fam}", 6, 65, 130, fam, NEAR, SPAN, how) for fam in ("peaky", "smooth")]
     return rows
+
+
+OFF_GRID = ("repeats", "beyond")
 
 
 CASES = parity_cases()
@@ -123,7 +130,7 @@ def _case_inputs(cid):
     _, n, Sp, S, fam, near, span, how = by_id(cid)
     seed = 2000 + 7 * S + 3 * Sp + n
     wp, zp = ray_batch(n, Sp, fam, near, span, seed)
-    w, z = fine_set(zp, S, fam, how, seed + 1)
+    w, z, zp = off_grid_inputs(zp, S, fam, how, seed + 1) if how in OFF_GRID else fine_set(zp, S, fam, how, seed + 1) + (zp,)
     scale = np.random.default_rng(seed + 2).uniform(0.5, 2.0, size=n).astype(F)
     return w, z, wp, zp, scale
 
@@ -161,3 +168,68 @@ def held(got, want, floors, label, report=print):
     report(f"| {label} | " + " | ".join(f"{names[k]} {e[k]:.2e} floor {floors[k]:.2e} gate {gate(floors[k]):.1e}" for k in range(3)) + " |")
     assert all(e[k] <= gate(floors[k]) for k in range(3)), (label, e, floors)
     return e
+
+
+# ---- inputs off the merged grid ------------------------------------------------------------------------------------------------------------
+N_REPEATS, N_REPEATS_PROP = 13, 6
+
+
+def off_grid_inputs(zp, S, family, how, seed):
+    """(w [n, S], z [n, S], zp) float32 for a proposal row set zp.
+    "repeats": the merged set, then 13 fine and 6 proposal depths a ray copied from their left neighbours (zero-width intervals inside a set,
+    where the two searches of a sample give lo > hi), the last two fine depths of every ray and the last two proposal depths of ray 0 equal
+    (a zero LAST width), sorted again; the weights are the merged set's, so a zero-width interval holds a weight.
+    "beyond": fine depths uniform in [z^_0 - span, z^_last + span], sorted: a third of them on either side overlap no proposal interval
+    (bound 0, q = w / (w + eps)), and the outer proposal intervals overlap several fine ones; the density's bump lies in the fine set's range."""
+    rng = np.random.default_rng(seed + 50)
+    n, Sp = zp.shape
+    if how == "repeats":
+        w, z = fine_set(zp, S, family, "merged", seed)
+        z, zp = z.copy(), zp.copy()
+        for r in range(n):
+            for row, count in ((z[r], N_REPEATS), (zp[r], N_REPEATS_PROP)):
+                for i in np.sort(1 + rng.permutation(len(row) - 3)[:count]):          # (increasing: a run of picks repeats one depth)
+                    row[i] = row[i - 1]
+            v = zp[r, np.nonzero(zp[r, 1:] == zp[r, :-1])[0][0]]                      # one repeat at the SAME depth in both sets: that is where lo > hi
+            i = min(int(np.searchsorted(z[r], v, side="left")), S - 4)
+            z[r, i], z[r, i + 1] = v, v
+        z[:, -1] = z[:, -2]
+        zp[0, -1] = zp[0, -2]
+        return w, np.sort(z, 1), np.sort(zp, 1)
+    assert how == "beyond"
+    z0 = zp[:, :1].astype(np.float64)
+    sp = (zp[:, -1:] - zp[:, :1]).astype(np.float64)
+    z = np.sort((z0 + sp * rng.uniform(-1.0, 2.0, size=(n, S))).astype(F), 1)
+    z64 = z.astype(np.float64)
+    lo, wide = z64[:, :1], z64[:, -1:] - z64[:, :1]
+    u = (z64 - lo) / wide
+    if family == "smooth":
+        sigma = rng.uniform(2.0, 8.0, size=(n, 1)) / wide * np.exp(-((u - rng.uniform(0.3, 0.7, size=(n, 1))) / 0.15) ** 2) * rng.uniform(0.5, 1.5, size=(n, S))
+    else:
+        sigma = np.where(rng.uniform(size=(n, S)) < min(1.0, 3.0 / S), rng.uniform(200.0, 4000.0, size=(n, S)) * S / wide, rng.uniform(0.0, 0.02, size=(n, S)) / wide)
+    return composite_weights(sigma, default_widths(z64)).astype(F), z, zp
+
+
+# ---- past the capped grid (tests.distortion_common has the sizes and `cycled`) ---------------------------------------------------------------
+LARGE_BASE = "P64_S65_N257_smooth"
+INF_FINE, ORDINARY, NAN_PROP = 0, 1, 130                 # the replaced rows of the base: INF_FINE and NAN_PROP are not live, ORDINARY is left as it is
+
+
+@functools.lru_cache(maxsize=None)
+def large_base():
+    """(w, z, wp, zp, dead [257], (loss, grad_prop, grad_fine) float64 without a ray_scale, floors) of the base batch: the case's rays with an
+    inf in the fine depths alone on one row, and a NaN in the proposal depths alone and NaN in both sets of weights on another."""
+    case = by_id(LARGE_BASE)
+    w, z, wp, zp, _ = (a.copy() for a in case_inputs(case))
+    z[INF_FINE, -1] = np.inf
+    zp[NAN_PROP, 17], w[NAN_PROP], wp[NAN_PROP] = np.nan, np.nan, np.nan
+    dead = ~(np.isfinite(z).all(1) & np.isfinite(zp).all(1))
+    return w, z, wp, zp, dead, reference(w, z, wp, zp)[:3], floor(case)
+
+
+def large_reference(n, scale):
+    """The float64 reference of the 257 base rows, cycled, times `scale`; zeros on the dead rows whatever `scale` holds there."""
+    from tests.distortion_common import cycled
+    dead, want = large_base()[4:6]
+    s = np.where(cycled(dead, n), 0.0, np.nan_to_num(np.asarray(scale, np.float64), nan=0.0))
+    return cycled(want[0], n) * s, cycled(want[1], n) * s[:, None], cycled(want[2], n) * s[:, None]

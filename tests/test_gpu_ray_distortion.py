@@ -67,6 +67,16 @@ def test_liveness(pattern):
     assert (L[~mask.any(1)] == 0).all()
 
 
+def test_liveness_at_the_sample_limit():
+    """S = 4096, live exactly in [100, 1000) and [3000, 4090): 31 whole dead chunks between live ones (pass 2 keeps its carries across all of
+    them), one in front and a short dead tail; NaN wherever a sample is not live."""
+    w, z, widths, live, scale, mask = dc.live_limit_case()
+    L, G = run(w, z, widths, live, scale)
+    assert np.isfinite(L).all() and np.isfinite(G).all() and (G[~mask] == 0).all() and not np.signbit(G[~mask]).any()
+    want, floors = dc.live_figures("limit")
+    dc.held(L, G, want, floors, "S4096 two patches")
+
+
 def test_a_missed_ray_is_exact_zeros_and_moves_no_other_bit():
     """Depths inf, weights 0 and ray_scale NaN on one ray of the batch: loss exactly 0, gradient row exactly 0, every other row the bits of the
     batch without that ray's values changed."""
@@ -128,6 +138,44 @@ def test_fixed_order():
     Ln, Gn = run(w, z, widths, None, None)
     L1, G1 = run(w, z, widths, None, np.ones(len(w), F))
     assert np.array_equal(Ln, L1) and np.array_equal(Gn, G1) and not np.array_equal(Ln, L)
+
+
+@pytest.fixture(scope="module")
+def base257():
+    """The 257 base rows through the kernel once, without a ray_scale: what every larger call has to repeat."""
+    w, z, dead, want, floors = dc.large_base()
+    L, G = run(w, z)
+    assert not L[dead].any() and not G[dead].any() and np.isfinite(L).all() and np.isfinite(G).all() and (np.abs(G[~dead]).max(1) > 0).all()
+    dc.held(L, G, want, floors, "the 257 base rows")
+    return L, G
+
+
+@pytest.mark.parametrize("n", dc.LARGE_N)
+def test_past_the_capped_grid(n, base257):
+    """8192 rays (the capped grid exactly), 8193 (one wave takes a second ray) and 16 389 (three passes for five waves), row k = base row
+    k mod 257, three base rows replaced by a missed ray, a ray finite in its first 30 samples and a ray of NaN weights: without a ray_scale
+    every row is bit for bit the 257-ray call's, the dead rows exact zeros; under a per-ray ray_scale (NaN on the dead rows) the cycled
+    float64 reference times that scale holds the call at the gate."""
+    w, z, dead, _, floors = dc.large_base()
+    W, Z, D = dc.cycled(w, n), dc.cycled(z, n), dc.cycled(dead, n)
+    L, G = run(W, Z)
+    assert np.array_equal(L, dc.cycled(base257[0], n)) and np.array_equal(G, dc.cycled(base257[1], n))
+    assert not L[D].any() and not G[D].any() and not np.signbit(G[D]).any() and D.sum() >= 2 * (n // 257)
+    scale = dc.large_scale(n, dead)
+    L, G = run(W, Z, scale=scale)
+    assert np.isfinite(L).all() and np.isfinite(G).all() and not L[D].any() and not G[D].any()
+    dc.held(L, G, dc.large_reference(n, scale), floors, f"N{n} cycled, ray_scale")
+
+
+def test_each_output_alone_past_the_capped_grid(base257):
+    """N = 8193: the loss alone and the gradient alone are the bits of the call that writes both."""
+    n = dc.LARGE_N[1]
+    w, z, _, _, _ = dc.large_base()
+    W, Z = dc.cycled(w, n), dc.cycled(z, n)
+    L1, none = run(W, Z, grad=False)
+    nothing, G1 = run(W, Z, loss=False)
+    assert none is None and nothing is None
+    assert np.array_equal(L1, dc.cycled(base257[0], n)) and np.array_equal(G1, dc.cycled(base257[1], n))
 
 
 # ---- 4. the op -----------------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import distortion_common as dc
 from tests import interlevel_common as ic
 
 pytestmark = pytest.mark.gpu
@@ -130,6 +131,44 @@ def test_fixed_order():
     with torch.cuda.stream(s):
         side = run(w, z, wp, zp, scale)
     assert same(side, got)
+
+
+@pytest.fixture(scope="module")
+def base257():
+    """The 257 base rows through the kernel once, without a ray_scale: what every larger call has to repeat."""
+    w, z, wp, zp, dead, want, floors = ic.large_base()
+    got = run(w, z, wp, zp)
+    assert all(np.isfinite(g).all() and not g[dead].any() for g in got) and (got[0][~dead] > 0).all()
+    ic.held(got, want, floors, "the 257 base rows")
+    return got
+
+
+@pytest.mark.parametrize("n", dc.LARGE_N)
+def test_past_the_capped_grid(n, base257):
+    """8192 rays (the capped grid exactly), 8193 (one wave takes a second ray and writes its `q_row` again) and 16 389 (three passes for five
+    waves), row k = base row k mod 257; one base row has an inf in its fine depths alone, one a NaN in its proposal depths alone and NaN
+    weights (the `continue` that skips the closing fence), so a wave that meets a dead ray goes on to a live one.  Without a ray_scale every
+    row is bit for bit the 257-ray call's, the dead rows exact zeros; under a per-ray ray_scale (NaN on the dead rows) the cycled float64
+    reference times that scale holds all three outputs at the gate."""
+    w, z, wp, zp, dead, _, floors = ic.large_base()
+    big = [dc.cycled(a, n) for a in (w, z, wp, zp)]
+    D = dc.cycled(dead, n)
+    got = run(*big)
+    assert same(got, [dc.cycled(g, n) for g in base257])
+    assert all(not g[D].any() and not np.signbit(g[D]).any() for g in got) and D.sum() >= 2 * (n // 257)
+    scale = dc.large_scale(n, dead)
+    got = run(*big, scale)
+    assert all(np.isfinite(g).all() and not g[D].any() for g in got)
+    ic.held(got, ic.large_reference(n, scale), floors, f"N{n} cycled, ray_scale")
+
+
+def test_each_output_alone_past_the_capped_grid(base257):
+    """N = 8193: each of the three outputs alone is the bits of the call that writes all of them."""
+    n = dc.LARGE_N[1]
+    big = [dc.cycled(a, n) for a in ic.large_base()[:4]]
+    for k, outs in enumerate([(1, 0, 0), (0, 1, 0), (0, 0, 1)]):
+        part = run(*big, outs=outs)
+        assert [p is None for p in part] == [not on for on in outs] and np.array_equal(part[k], dc.cycled(base257[k], n)), outs
 
 
 def test_the_op_on_a_side_stream_gives_the_default_streams_bits():

@@ -76,6 +76,59 @@ def test_liveness_patterns_are_what_they_say(pattern):
         assert max(dc.rel_linf(got[0], want[0]), dc.rel_linf(got[1], want[1])) <= dc.FLOOR_GUARD
 
 
+def test_the_patch_patterns_have_their_dead_chunks_where_they_say():
+    """What an instanced step produces: a whole dead chunk between live ones, whole dead chunks behind the last live sample, patches that
+    end on the chunk edges, two short patches -- each with live samples on both sides of what is dead, and a gradient worth the name."""
+    m = {p: dc.live_case(p)[5] for p in dc.PATCH_PATTERNS}
+    assert dc.LIVE_PATTERNS[:4] == ["all_dead", "one_in_last_chunk", "first_behind_chunk0", "random35"] and dc.LIVE_PATTERNS[4:] == dc.PATCH_PATTERNS
+    a = m["dead_chunk_between"]
+    assert not a[:, 64:128].any() and a[:, 5].all() and a[:, 190].all() and 0.4 < a[:, :64].mean() < 0.8 and 0.4 < a[:, 128:].mean() < 0.8
+    a = m["dead_tail"]
+    assert not a[:, 70:].any() and a[:, 3].all() and a[:, 69].all() and 0.5 < a[:, :70].mean() < 0.9
+    a = m["patch_ends_on_chunk_edges"]
+    assert (a.sum(1) == 27 + 64).all() and a[:, 37:64].all() and a[:, 128:192].all()
+    a = m["two_short_patches"]
+    assert (a.sum(1) == 7).all() and a[:, 10:14].all() and a[:, 150:153].all()
+    for p in dc.PATCH_PATTERNS:
+        want, floors = dc.live_figures(p)
+        print(f"| {p} | floor of the loss {floors[0]:.2e} | of the gradient {floors[1]:.2e} | max |grad| {np.abs(want[1]).max():.3e} |")
+        assert max(floors) <= dc.FLOOR_GUARD and np.abs(want[1]).max() > 1e-3 and (np.abs(want[0]) > 0).all()
+
+
+def test_the_case_at_the_sample_limit_is_inside_the_guard():
+    """S = 4096, live exactly [100, 1000) and [3000, 4090): 31 dead chunks between live ones; NaN where not live; the floors <= FLOOR_GUARD."""
+    w, z, widths, live, scale, mask = dc.live_limit_case()
+    assert mask.shape == (3, 4096) and (mask.sum(1) == 900 + 1090).all() and mask[:, 100:1000].all() and mask[:, 3000:4090].all()
+    assert not mask.reshape(3, 64, 64)[:, 16:46].any() and np.array_equal(dc.live_mask(z, live), mask)
+    assert np.isnan(w[~mask]).all() and np.isnan(z[~mask]).all() and np.isnan(widths[~mask]).all() and np.isfinite(w[mask]).all()
+    want, floors = dc.live_figures("limit")
+    print(f"| S4096 two patches | floor of the loss {floors[0]:.2e} | of the gradient {floors[1]:.2e} | max |grad| {np.abs(want[1]).max():.3e} |")
+    assert np.isfinite(want[0]).all() and np.isfinite(want[1]).all() and (want[1][~mask] == 0).all()
+    assert max(floors) <= dc.FLOOR_GUARD and dc.gate(max(floors)) < dc.CAP and np.abs(want[1]).max() > 1e-3
+
+
+def test_the_large_batches_cycle_a_base_whose_rows_meet_every_wave():
+    """The base of the calls past the capped grid: 257 rows (prime; 8192 mod 257 = 225, so a wave meets another base row in every pass), two
+    of them without a live sample and one live in its first 30 samples only; the reference is zeros where it has to be and inside the guard."""
+    w, z, dead, (loss, grad), floors = dc.large_base()
+    assert len(w) == 257 and dc.GRID_RAYS == 8192 and dc.GRID_RAYS % 257 == 225 and dc.LARGE_N == [8192, 8193, 16389]
+    assert np.array_equal(np.nonzero(dead)[0], [dc.MISSED, dc.NAN_W]) and np.isnan(w[dc.NAN_W]).all() and not np.isfinite(z[dc.NAN_W]).any()
+    assert np.isfinite(z[dc.PARTIAL, :30]).all() and not np.isfinite(z[dc.PARTIAL, 30:]).any()
+    assert np.isfinite(loss).all() and np.isfinite(grad).all() and not loss[dead].any() and not grad[dead].any() and not grad[dc.PARTIAL, 30:].any()
+    assert (loss[~dead] > 0).all() and max(floors) <= dc.FLOOR_GUARD
+    f32 = dc.linear_form(w, z)
+    assert max(dc.rel_linf(f32[0], loss), dc.rel_linf(f32[1], grad)) <= dc.FLOOR_GUARD
+    for n in dc.LARGE_N:
+        rows = np.arange(n) % 257
+        if n > dc.GRID_RAYS:                                                      # the second ray of a wave is another base row; a dead one is followed by a live one
+            assert (rows[dc.GRID_RAYS:] != rows[:n - dc.GRID_RAYS]).all() and not dead[rows[dc.GRID_RAYS:][dead[rows[:n - dc.GRID_RAYS]]]].any()
+        scale = dc.large_scale(n, dead)
+        L, G = dc.large_reference(n, scale)
+        assert np.isnan(scale[dead[rows]]).all() and np.isfinite(scale[~dead[rows]]).all() and np.isfinite(L).all() and np.isfinite(G).all()
+        k = n - 1                                                                 # the last ray: the base row its index names, times its own scale
+        assert not dead[rows[k]] and L[k] == loss[rows[k]] * np.float64(scale[k]) and np.array_equal(G[k], grad[rows[k]] * np.float64(scale[k]))
+
+
 def test_without_the_shift_float32_loses_its_digits():
     """near = 500, span 0.5, S = 256: the unshifted float32 form is beyond 1e-4, the shifted one inside 2.5e-5 -- why the shift is specified."""
     w, z, widths, scale = dc.case_inputs(dc.NEAR500)

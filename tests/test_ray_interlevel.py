@@ -86,6 +86,47 @@ def test_ties_are_everywhere_in_the_merged_cases():
     assert not any(np.isin(zp[r], z[r]).any() for r in range(len(z)))
 
 
+@pytest.mark.parametrize("fam", ["peaky", "smooth"])
+def test_the_off_grid_cases_are_what_they_say(fam):
+    """"repeats": exact repeats inside either set (13 + the last pair a fine row, 6 a proposal row, ray 0's last proposal width zero), so that
+    a sample's two searches give lo > hi somewhere; "beyond": a third of the fine samples on either side of the proposal's range, where nothing
+    bounds them.  Both sorted, finite, and the dense torch statement agrees with the reference."""
+    w, z, wp, zp, _ = ic.case_inputs(ic.by_id(f"P65_S130_N6_repeats_{fam}"))
+    assert (np.diff(z, axis=1) >= 0).all() and (np.diff(zp, axis=1) >= 0).all()
+    assert ((np.diff(z, axis=1) == 0).sum(1) >= 10).all() and ((np.diff(zp, axis=1) == 0).sum(1) >= 4).all()
+    assert (z[:, -1] == z[:, -2]).all() and zp[0, -1] == zp[0, -2] and (zp[1:, -1] > zp[1:, -2]).all()
+    b, bp = ic.interval_ends(z), ic.interval_ends(zp)
+    crossed = [(np.searchsorted(bp[r], z[r], side="right") > np.searchsorted(zp[r], b[r], side="left")).sum() for r in range(len(z))]
+    crossed_prop = [(np.searchsorted(b[r], zp[r], side="right") > np.searchsorted(z[r], bp[r], side="left")).sum() for r in range(len(z))]
+    assert min(crossed) >= 1 and min(crossed_prop) >= 1, (crossed, crossed_prop)
+    w, z, wp, zp, _ = ic.case_inputs(ic.by_id(f"P65_S130_N6_beyond_{fam}"))
+    assert (np.diff(z, axis=1) >= 0).all()
+    below, above = (z < zp[:, :1]).sum(1), (z > ic.interval_ends(zp)[:, -1:]).sum(1)
+    assert (below >= 25).all() and (above >= 25).all() and ((z > zp[:, :1]) & (z < zp[:, -1:])).sum(1).min() >= 25, (below, above)
+    q = ic.case_reference(ic.by_id(f"P65_S130_N6_beyond_{fam}"))[3]
+    assert all(q[r, :below[r] - 1].max() > 0.99 for r in range(len(z)))                                     # nothing bounds a sample in front of the proposal's range
+
+
+def test_the_large_batches_cycle_a_base_whose_rows_meet_every_wave():
+    """The base of the calls past the capped grid: two of its 257 rows are not live (an inf in the fine depths alone; a NaN in the proposal
+    depths alone with NaN weights), the row between them in index is ordinary; zeros where they have to be, inside the guard, worth the name."""
+    from tests import distortion_common as dc
+    w, z, wp, zp, dead, want, floors = ic.large_base()
+    assert len(w) == 257 and np.array_equal(np.nonzero(dead)[0], [ic.INF_FINE, ic.NAN_PROP]) and not dead[ic.ORDINARY]
+    assert np.isinf(z[ic.INF_FINE]).sum() == 1 and np.isfinite(zp[ic.INF_FINE]).all() and np.isfinite(w[ic.INF_FINE]).all()
+    assert np.isnan(zp[ic.NAN_PROP]).sum() == 1 and np.isfinite(z[ic.NAN_PROP]).all() and np.isnan(w[ic.NAN_PROP]).all() and np.isnan(wp[ic.NAN_PROP]).all()
+    assert all(np.isfinite(g).all() and not g[dead].any() for g in want) and (want[0][~dead] > 0).all() and max(floors) <= ic.FLOOR_GUARD
+    f32 = ic.reference(w, z, wp, zp, dtype=ic.F)
+    assert max(ic.rel_linf(f32[k], want[k]) for k in range(3)) <= ic.FLOOR_GUARD
+    for n in dc.LARGE_N:
+        scale = dc.large_scale(n, dead)
+        got = ic.large_reference(n, scale)
+        rows = np.arange(n) % 257
+        assert np.isnan(scale[dead[rows]]).all() and all(np.isfinite(g).all() and not g[dead[rows]].any() for g in got)
+        k = n - 1
+        assert not dead[rows[k]] and all(np.array_equal(g[k], x[rows[k]] * np.float64(scale[k])) for g, x in zip(got, want))
+
+
 def test_a_ray_that_is_not_live_is_zeros_in_the_reference():
     w, z, wp, zp, scale = (a.copy() for a in ic.case_inputs(ic.by_id("P8_S16_N9_smooth")))
     z[2], zp[2], w[2], scale[2] = np.inf, np.inf, np.nan, np.nan
